@@ -11,8 +11,16 @@ classes, their streams and the HIP graph it replays. Ranks (one process per
 GPU) run the parts of the library's root partition, so the total work per
 step is fixed: scaling "strong"; for N > 1 the digest records are
 all-gathered over RCCL each step. The digests are poisoned before the timed
-loop and the last timed step's digests are checked against the CPU
-restatements on a role-stratified root set (`parity_vs_cpu_sample`).
+loop.
+
+A plain run sets up, warms up, times the steps and prints the one JSON line
+(`value`, `ms_per_step`, the workload's config). `--full` adds, after the
+timed steps, everything else: the last timed step's digests checked against
+the CPU restatements on a role-stratified root set (`parity_vs_cpu_sample`),
+the CPU baseline, the per-launch roofline with the store probe, the first
+sweep after a graph change, `gpu_busy`, and --ab / --dist-parity.
+`--dump-outputs DIR` writes what the last timed step computed (every root's
+digest, the dist / next-hop rows of a fixed seeded sample) as DIR/*.npy.
 
 Other topologies (parity / side benches, not the headline): fabric10k,
 fabric100k-w and fabric10k-w (metrics 1..64, seed 7: the weighted cover
@@ -20,6 +28,7 @@ path), grid31, grid100 (unit 100x100 grid, diameter 198), mesh1m (8,192
 sampled roots on the per-class batch driver).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--topology T]
+                       [--full] [--dump-outputs DIR]
        torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
                 --master-port P bench.py --gpus N ...
 Profiling mode (one class alone, R launches on one stream, no JSON line):
@@ -28,6 +37,7 @@ Profiling mode (one class alone, R launches on one stream, no JSON line):
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -192,6 +202,70 @@ class BusySampler:
 BUSY = {}
 
 
+def busy_sampler(args):
+    """The timed region's context: the gpu_busy sampler under --full only."""
+    return BusySampler(torch.cuda.current_device()) if args.full else contextlib.nullcontext()
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy payload per --dump-outputs (the limit is 64 MB)
+DUMP_ROOTS_PER_WIDTH = 4
+DUMP_NODES = 16384
+
+
+def u64_words(a) -> np.ndarray:
+    """[..., k] u64 -> [..., 2k] float64 of (low, high) 32-bit halves: exact in float64."""
+    a = np.ascontiguousarray(a, np.uint64)
+    return a.view(np.uint32).astype(np.float64).reshape(a.shape[:-1] + (2 * a.shape[-1],))
+
+
+def dump_sample(V: int, roots, widths):
+    """The fixed sample --dump-outputs writes rows for: up to DUMP_ROOTS_PER_WIDTH
+    roots of every next-hop width (`widths`: words per root; seed 0x5eed, drawn
+    from the sorted roots), narrowest first while the rows fit DUMP_BUDGET, and
+    the destination nodes: all when V <= DUMP_NODES, else DUMP_NODES drawn
+    likewise. -> (roots [k] u32 sorted by (width, id), nodes [m] sorted)"""
+    rng = np.random.default_rng(SEED)
+    nodes = np.arange(V, dtype=np.int64) if V <= DUMP_NODES else \
+        np.sort(rng.choice(V, DUMP_NODES, replace=False)).astype(np.int64)
+    roots, widths = np.asarray(roots, np.uint32), np.asarray(widths, np.int64)
+    roots, first = np.unique(roots, return_index=True)
+    widths = widths[first]
+    pick, budget = [], DUMP_BUDGET
+    for w in sorted(set(widths.tolist())):
+        m = roots[widths == w]
+        for r in np.sort(rng.choice(m, min(DUMP_ROOTS_PER_WIDTH, m.size), replace=False)).tolist():
+            need = 8 * nodes.size * (1 + w)
+            if need <= budget:
+                budget -= need
+                pick.append((w, r))
+    return np.array([r for _, r in pick], np.uint32), nodes
+
+
+def dump_outputs(out_dir: str, step_digest: dict, roots, nodes, dist_rows, nh_rows):
+    """DIR/<name>.npy, float64 (u32 values are exact): `digest_roots` [n] and
+    `digest` [n, 6] (the 3 u64 digest words of every root as low / high
+    halves, by root id); `roots` [k], `nodes` [m], `dist` [k, m]; per
+    next-hop width W `nh_w<W>_roots` [k_W] and `nh_w<W>` [k_W, m, W]: the
+    sampled roots' rows at the sampled nodes (nh_rows entries may be None)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ids = np.array(sorted(step_digest), np.int64)
+    dig = np.stack([step_digest[int(r)] for r in ids]) if ids.size else np.zeros((0, 3), np.uint64)
+    out = {"digest_roots": ids.astype(np.float64), "digest": u64_words(dig),
+           "roots": roots.astype(np.float64), "nodes": nodes.astype(np.float64),
+           "dist": np.stack(dist_rows).astype(np.float64) if dist_rows else
+           np.zeros((0, nodes.size))}
+    for w in sorted(set(nh.shape[-1] for nh in nh_rows if nh is not None)):
+        sel = [i for i, nh in enumerate(nh_rows) if nh is not None and nh.shape[-1] == w]
+        out[f"nh_w{w}_roots"] = roots[sel].astype(np.float64)
+        out[f"nh_w{w}"] = np.stack([nh_rows[i] for i in sel]).astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, f"dump of {total} bytes"
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"dump-outputs: {len(out)} arrays, {sum(a.nbytes for a in out.values()) / 2**20:.1f} MiB "
+        f"in {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -246,7 +320,20 @@ def main():
                     help='sweeps: in-process A/B of engine env knobs, e.g. "OSPF_LEAF_CTILES=20;'
                          'OSPF_LEAF_GROUP_MAJOR=1" (variants ";"-separated, settings ",")')
     ap.add_argument("--ab-rounds", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take the side measurements and checks: "
+                         "per-launch roofline, store probe, first sweep after a graph change, "
+                         "gpu_busy sampling, CPU baseline and parity of the timed step's digests "
+                         "(and --ab / --dist-parity); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the last timed step computed as "
+                         "DIR/<name>.npy (float64): every root's digest and the dist / next-hop "
+                         "rows of a fixed, seeded sample of roots")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and (args.ab or args.dist_parity > 0):
+        ap.error("--ab and --dist-parity are side measurements: pass --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -390,7 +477,7 @@ def main():
     if dist_on:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    with BusySampler(torch.cuda.current_device()):
+    with busy_sampler(args):
         t_start = time.perf_counter()
         for i in range(args.steps):
             step(args.warmup + i, True)
@@ -421,7 +508,40 @@ def main():
                     step_digest[int(root)] = d[j]
 
     roots_total = B_all * args.steps if weak else pool.size * args.steps
+    for c in classes:
+        c.extra["ms"] = [a_.elapsed_time(b_) for a_, b_ in c.extra["ev"]]
 
+    if args.dump_outputs and rank == 0:  # this rank's rows of the last timed step
+        mine = [(int(r), c, j) for c in classes for j, r in
+                enumerate(c.extra["mine"] if not weak else c.extra["roots"].cpu().numpy())]
+        s_roots, nodes = dump_sample(V, [m[0] for m in mine], [m[1].nh_words for m in mine])
+        at = {m[0]: m for m in mine}
+        d_nodes = torch.from_numpy(nodes).to(dev)
+        dist_rows, nh_rows = [], []
+        for r in s_roots.tolist():
+            _, c, j = at[r]
+            dist_rows.append(c.extra["dist"][j][d_nodes].cpu().numpy().view(np.uint32))
+            nh_rows.append(None if c.extra["nh"] is None else
+                           c.extra["nh"][j][d_nodes].cpu().numpy().view(np.uint32))
+        dump_outputs(args.dump_outputs, step_digest, s_roots, nodes, dist_rows, nh_rows)
+
+    roofline = batch_roofline(args, eng, classes, V, E, weighted, dev, launch) \
+        if args.full else None
+    classes_cfg = [{"cap": c.cap, "nh_words": c.nh_words, "roots_this_rank": c.extra["n"],
+                    **{kk: c.extra["plan"][kk] for kk in ("variant", "slices", "block")},
+                    "avg_launch_ms": round(float(np.mean(c.extra["ms"])), 3),
+                    "isolated_launch_ms": round(c.extra["iso_ms"], 3) if args.full else None}
+                   for c in classes]
+    report(args, stream, names, csr, step_digest, dt, roots_total, E, desc, n_roots, V, world,
+           rank, dist_on, backend, int(B_all if weak else pool.size), classes_cfg, roofline,
+           "weak" if weak else "strong", "batch", pool=pool)
+    if dist_on:
+        torch.distributed.destroy_process_group()
+
+
+def batch_roofline(args, eng, classes, V, E, weighted, dev, launch):
+    """--full, per-class batch driver: every class launched alone after the
+    timed steps (sets extra["iso_ms"]) -> the roofline record."""
     # roofline. The classes overlap on their streams inside the timed steps,
     # so each class is then timed ALONE (not part of `value`): R launches on
     # one stream bracketed by HIP events on that stream. A class launch is a
@@ -440,7 +560,6 @@ def main():
                 b_.synchronize()
                 ms.append(a_.elapsed_time(b_))
         x["iso_ms"] = float(np.median(ms[1:])) if len(ms) > 1 else float(ms[0])
-        x["ms"] = [a_.elapsed_time(b_) for a_, b_ in x["ev"]]
     eng.sync(iso_s.cuda_stream)
 
     def class_roofline(c):
@@ -482,16 +601,7 @@ def main():
                 "beat (not a roofline fraction); traffic = measured HBM bytes per launch "
                 "(rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, profiles/<round>/pmc_traffic.json)",
     }
-
-    classes_cfg = [{"cap": c.cap, "nh_words": c.nh_words, "roots_this_rank": c.extra["n"],
-                    **{kk: c.extra["plan"][kk] for kk in ("variant", "slices", "block")},
-                    "avg_launch_ms": round(float(np.mean(c.extra["ms"])), 3),
-                    "isolated_launch_ms": round(c.extra["iso_ms"], 3)} for c in classes]
-    report(args, stream, names, csr, step_digest, dt, roots_total, E, desc, n_roots, V, world,
-           rank, dist_on, backend, int(B_all if weak else pool.size), classes_cfg, roofline,
-           "weak" if weak else "strong", "batch", pool=pool)
-    if dist_on:
-        torch.distributed.destroy_process_group()
+    return roofline
 
 
 def sweep_main(args, eng, csr, names, stream, desc, V, E, world, rank, dist_on, dev, backend,
@@ -545,7 +655,7 @@ def sweep_main(args, eng, csr, names, stream, desc, V, E, world, rank, dist_on, 
     if dist_on:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    with BusySampler(torch.cuda.current_device()):
+    with busy_sampler(args):
         t_start = time.perf_counter()
         for _ in range(args.steps):
             step()
@@ -567,12 +677,59 @@ def sweep_main(args, eng, csr, names, stream, desc, V, E, world, rank, dist_on, 
             for j, root in enumerate(groots[r]):
                 if root >= 0:
                     step_digest[int(root)] = g[r, j]
-    else:
+    elif args.full or args.dump_outputs:
         sw.digests_dev(gbuf.data_ptr(), main_s.cuda_stream)
         d = gbuf.cpu().numpy().view(np.uint64)
         for j, root in enumerate(sw.roots):
             step_digest[int(root)] = d[j]
 
+    if args.dump_outputs and rank == 0:  # rows as ospf_sweep_copy_rows hands them to a caller
+        words = shard.nh_words_of(csr["row_ptr"], csr["col"])
+        s_roots, nodes = dump_sample(V, sw.roots, words[sw.roots])
+        rows = [sw.rows([r]) for r in s_roots.tolist()]
+        dump_outputs(args.dump_outputs, step_digest, s_roots, nodes,
+                     [d_[0][nodes] for d_, _ in rows], [nh[0][nodes] for _, nh in rows])
+
+    cfg = {"mode": sw.mode, "hip_graph": sw.hip_graph, "roots_this_rank": n,
+           "rows_this_rank": sw.n_rows, "device_bytes": sw.device_bytes,
+           "closure_over_roots": round(sw.n_rows / max(1, n), 4),
+           "sweep_create_ms": round(create_s * 1e3, 1),
+           "sweep_create_note": "ospf_sweep_create: host plan (partition, leaf set, twin "
+                                "classes, row positions), allocation, one eager run and the HIP "
+                                "graph capture; paid once per graph version, not in `value`"}
+    trav = sw.step_traversed_edges
+    sw_roots = sw.roots.copy()
+    roofline = sweep_full(args, eng, sw, cfg, dt, V, mode, part, n_parts, main_s, step_digest) \
+        if args.full else None
+    sw.close()
+    if K > 1:  # one part per rank of a K x N partition: the parts' roots, not V
+        tot = n
+        if dist_on:
+            t = torch.tensor([n], dtype=torch.int64, device=coll_dev)
+            torch.distributed.all_reduce(t)
+            tot = int(t.item())
+        cfg["part_of"] = {"parts": n_parts, "part_of_rank0": (K // 2) * world,
+                          "roots_all_ranks": tot,
+                          "note": "a contiguous block of the all-sources sweep's root partition "
+                                  "(each width class in largest-neighbour order, cut into "
+                                  "n_parts slices); value = its roots / step time"}
+        report(args, stream, names, csr, step_digest, dt, tot * args.steps, E, desc, tot, V,
+               world, rank, dist_on, backend, tot, cfg, roofline, "strong", "sweep:" + cfg["mode"],
+               pool=np.sort(sw_roots), trav_edges=trav * args.steps,
+               scope=f" part {(K // 2) * world} .. +{world} of {n_parts} of the all-sources sweep "
+                     f"({tot} roots)")
+    else:
+        report(args, stream, names, csr, step_digest, dt, V * args.steps, E, desc, 0, V, world,
+               rank, dist_on, backend, V, cfg, roofline, "strong", "sweep:" + cfg["mode"],
+               trav_edges=trav * args.steps)
+    if dist_on:
+        torch.distributed.destroy_process_group()
+
+
+def sweep_full(args, eng, sw, cfg, dt, V, mode, part, n_parts, main_s, step_digest):
+    """--full, sweep path: after the timed steps every launch alone (the
+    roofline), the first sweep after a graph change (into cfg), the store
+    probe and --ab; closes `sw` on the way. -> the roofline record."""
     # every launch alone on its stream (HIP events there, inside the library)
     prof = sw.profile(args.iso_reps)
     units = []
@@ -607,14 +764,6 @@ def sweep_main(args, eng, csr, names, stream, desc, V, E, world, rank, dist_on, 
                 "sweep's compulsory bytes / ms_per_step. traffic = measured HBM bytes per launch "
                 "(rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, profiles/<round>/pmc_traffic.json)",
     }
-    cfg = {"mode": sw.mode, "hip_graph": sw.hip_graph, "roots_this_rank": n,
-           "rows_this_rank": sw.n_rows, "device_bytes": sw.device_bytes,
-           "closure_over_roots": round(sw.n_rows / max(1, n), 4),
-           "sweep_create_ms": round(create_s * 1e3, 1),
-           "sweep_create_note": "ospf_sweep_create: host plan (partition, leaf set, twin "
-                                "classes, row positions), allocation, one eager run and the HIP "
-                                "graph capture; paid once per graph version, not in `value`"}
-    trav = sw.step_traversed_edges
     sw_roots = sw.roots.copy()
     sw.close()
     # what a production caller pays once per graph version (odl::LinkState:
@@ -645,28 +794,7 @@ def sweep_main(args, eng, csr, names, stream, desc, V, E, world, rank, dist_on, 
             roofline["frac_of_box_store_rate"] = round(dom["achieved"] / best, 4)
     if args.ab:
         roofline["ab"] = ab_sweeps(args, eng, mode, part, n_parts, main_s, step_digest, sw_roots)
-    if K > 1:  # one part per rank of a K x N partition: the parts' roots, not V
-        tot = n
-        if dist_on:
-            t = torch.tensor([n], dtype=torch.int64, device=coll_dev)
-            torch.distributed.all_reduce(t)
-            tot = int(t.item())
-        cfg["part_of"] = {"parts": n_parts, "part_of_rank0": (K // 2) * world,
-                          "roots_all_ranks": tot,
-                          "note": "a contiguous block of the all-sources sweep's root partition "
-                                  "(each width class in largest-neighbour order, cut into "
-                                  "n_parts slices); value = its roots / step time"}
-        report(args, stream, names, csr, step_digest, dt, tot * args.steps, E, desc, tot, V,
-               world, rank, dist_on, backend, tot, cfg, roofline, "strong", "sweep:" + cfg["mode"],
-               pool=np.sort(sw_roots), trav_edges=trav * args.steps,
-               scope=f" part {(K // 2) * world} .. +{world} of {n_parts} of the all-sources sweep "
-                     f"({tot} roots)")
-    else:
-        report(args, stream, names, csr, step_digest, dt, V * args.steps, E, desc, 0, V, world,
-               rank, dist_on, backend, V, cfg, roofline, "strong", "sweep:" + cfg["mode"],
-               trav_edges=trav * args.steps)
-    if dist_on:
-        torch.distributed.destroy_process_group()
+    return roofline
 
 
 def store_probe(eng, V: int, dom: dict, args):
@@ -761,8 +889,9 @@ def parity_sample(csr, V: int, k: int = 256):
 def report(args, stream, names, csr, step_digest, dt, roots_total, E, desc, n_roots, V, world,
            rank, dist_on, backend, roots_per_step, classes_cfg, roofline, scaling, mode,
            pool=None, trav_edges=None, scope=None):
-    """CPU baseline + parity of the timed step's digests (rank 0) and the one
-    JSON line. gteps = edges the traversal kernels relaxed (trav_edges over
+    """The one JSON line (rank 0), under --full after the CPU baseline and the
+    parity of the timed step's digests.
+    gteps = edges the traversal kernels relaxed (trav_edges over
     the timed steps; every root of a per-root / batch path traverses E) / t;
     gteps_all_pairs_equiv = roots x E_dir / t, what per-root SSSPs would have
     to relax for the same rows (derived rows relax none)."""
@@ -773,8 +902,8 @@ def report(args, stream, names, csr, step_digest, dt, roots_total, E, desc, n_ro
     perm = np.random.default_rng(SEED).permutation(V).astype(np.uint32)
     if pool is None:
         pool = perm
-    strat = parity_sample(csr, V) if n_roots <= 0 else pool[:256]
-    if rank == 0 and world == 1 and not args.no_cpu:
+    strat = pool[:256] if n_roots > 0 else parity_sample(csr, V) if args.full else None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import Oracle  # CPU baseline leg only (the restatements under oracle/)
         threads = args.cpu_threads or host_threads()
         k = args.cpu_sample if args.cpu_sample >= 0 else (16 if args.topology == "mesh1m" else 256)

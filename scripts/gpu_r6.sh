@@ -5,8 +5,8 @@
 #   scale   tests/test_gpu_scale.py only
 #   scale4  tests/test_gpu_scale_sweeps.py (full-size sweeps with drains / weights)
 #   t       pytest $TESTS;  script  python $SCRIPT
-#   bench   python bench.py (default headline config)
-#   benchT  python bench.py --topology $TOPO
+#   bench   python bench.py --full (default headline config)
+#   benchT  python bench.py --full --topology $TOPO
 #   prof    rocprofv3 --kernel-trace --stats of a short bench
 # Each GPU step has its own time limit; the first failure ends the call.
 set -u
@@ -21,35 +21,35 @@ for st in $STEPS; do
            tail -5 "$OUT/gpu.log";;
     scale) timeout -k 10 900 $PYT -s tests/test_gpu_scale.py ${SCALE_K:+-k "$SCALE_K"} > "$OUT/scale.log" 2>&1; rc=$?
            tail -8 "$OUT/scale.log";;
-    bench) timeout -k 10 420 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
+    bench) timeout -k 10 420 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
            cat "$OUT/bench.json"; tail -3 "$OUT/bench.err";;
-    benchT) timeout -k 10 600 python bench.py --topology $TOPO ${BENCH_ARGS:-} > "$OUT/bench_$TOPO.json" 2> "$OUT/bench_$TOPO.err"; rc=$?
+    benchT) timeout -k 10 600 python bench.py --full --topology $TOPO ${BENCH_ARGS:-} > "$OUT/bench_$TOPO.json" 2> "$OUT/bench_$TOPO.err"; rc=$?
            cat "$OUT/bench_$TOPO.json"; tail -3 "$OUT/bench_$TOPO.err";;
     prof)  timeout -k 10 420 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-             python bench.py --steps 5 --warmup 1 --no-cpu ${PROF_ARGS:-} > "$OUT/prof_bench.json" 2> "$OUT/prof.err"; rc=$?
+             python bench.py --full --steps 5 --warmup 1 --no-cpu ${PROF_ARGS:-} > "$OUT/prof_bench.json" 2> "$OUT/prof.err"; rc=$?
            tail -3 "$OUT/prof.err";;
     csv)   timeout -k 10 420 rocprofv3 --kernel-trace --stats -d "$OUT/csv" -o run --output-format csv -- \
-             python bench.py --steps 5 --warmup 1 --no-cpu ${PROF_ARGS:-} > "$OUT/csv_bench.json" 2> "$OUT/csv.err"; rc=$?
+             python bench.py --full --steps 5 --warmup 1 --no-cpu ${PROF_ARGS:-} > "$OUT/csv_bench.json" 2> "$OUT/csv.err"; rc=$?
            tail -2 "$OUT/csv.err";;
     pmc)   rc=0; i=0
            for P in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_VALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY"; do
              i=$((i+1))
              timeout -s KILL 120 rocprofv3 --pmc $P -d "$OUT/pmc$i" -o run --output-format csv -- \
-               python bench.py --steps 1 --warmup 0 --no-cpu --iso-reps 1 ${PROF_ARGS:-} > "$OUT/pmc$i.log" 2>&1; rc=$?
+               python bench.py --full --steps 1 --warmup 0 --no-cpu --iso-reps 1 ${PROF_ARGS:-} > "$OUT/pmc$i.log" 2>&1; rc=$?
              echo "pmc pass $i rc=$rc"; [ $rc -eq 0 ] || break
            done
            [ $rc -eq 0 ] && python scripts/pmc_by_kernel.py "$OUT"/pmc* > "$OUT/pmc_by_kernel.json";;
     unitprof)  # per-launch-unit kernel time + HBM traffic of the sweep (scripts/sweep_unit_stats.py)
            timeout -k 10 420 rocprofv3 --kernel-trace --stats -d "$OUT/utrace" -o run --output-format csv -- \
-             python bench.py --steps 5 --warmup 1 --no-cpu --iso-reps 3 ${PROF_ARGS:-} > "$OUT/utrace_bench.json" 2> "$OUT/utrace.err"; rc=$?
+             python bench.py --full --steps 5 --warmup 1 --no-cpu --iso-reps 3 ${PROF_ARGS:-} > "$OUT/utrace_bench.json" 2> "$OUT/utrace.err"; rc=$?
            [ $rc -eq 0 ] && OSPF_LV_SERIAL=1 timeout -k 10 420 rocprofv3 --kernel-trace --stats -d "$OUT/utrace_serial" -o run --output-format csv -- \
-             python bench.py --steps 2 --warmup 1 --no-cpu --iso-reps 3 ${PROF_ARGS:-} > "$OUT/utrace_serial_bench.json" 2>> "$OUT/utrace.err"; rc=$?
+             python bench.py --full --steps 2 --warmup 1 --no-cpu --iso-reps 3 ${PROF_ARGS:-} > "$OUT/utrace_serial_bench.json" 2>> "$OUT/utrace.err"; rc=$?
            i=0
            for P in FETCH_SIZE WRITE_SIZE; do
              [ $rc -eq 0 ] || break
              i=$((i+1))
              timeout -s KILL 180 rocprofv3 --pmc $P -d "$OUT/upmc$i" -o run --output-format csv -- \
-               python bench.py --steps 1 --warmup 0 --no-cpu --iso-reps 1 ${PROF_ARGS:-} > "$OUT/upmc$i.json" 2> "$OUT/upmc$i.err"; rc=$?
+               python bench.py --full --steps 1 --warmup 0 --no-cpu --iso-reps 1 ${PROF_ARGS:-} > "$OUT/upmc$i.json" 2> "$OUT/upmc$i.err"; rc=$?
              echo "pmc pass $P rc=$rc"
            done
            if [ $rc -eq 0 ]; then
@@ -59,13 +59,13 @@ for st in $STEPS; do
            fi;;
     upmcsq)  # per-unit SQ counters (instructions, busy / wait cycles) of the sweep
            timeout -s KILL 180 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY -d "$OUT/upmcsq" -o run --output-format csv -- \
-             python bench.py --steps 1 --warmup 0 --no-cpu --iso-reps 1 ${PROF_ARGS:-} > "$OUT/upmcsq.json" 2> "$OUT/upmcsq.err"; rc=$?
+             python bench.py --full --steps 1 --warmup 0 --no-cpu --iso-reps 1 ${PROF_ARGS:-} > "$OUT/upmcsq.json" 2> "$OUT/upmcsq.err"; rc=$?
            [ $rc -eq 0 ] && python scripts/sweep_unit_stats.py --bench "$OUT/upmcsq.json" --pmc "$OUT/upmcsq" --reps 1 --out "$OUT/pmc_sq.json" > /dev/null; rc=$?;;
     ab)    # A/B of env knobs on the default bench: AB="NAME=1 OTHER=1 ..." (one run each + baseline)
            rc=0
            for kv in base ${AB:-}; do
              if [ "$kv" = base ]; then E=""; else E="${kv//,/ }"; fi
-             timeout -k 10 300 env $E python bench.py --steps 20 --warmup 2 --cpu-sample 8 --iso-reps 2 ${AB_ARGS:-} > "$OUT/ab_$kv.json" 2> "$OUT/ab_$kv.err"; rc=$?
+             timeout -k 10 300 env $E python bench.py --full --steps 20 --warmup 2 --cpu-sample 8 --iso-reps 2 ${AB_ARGS:-} > "$OUT/ab_$kv.json" 2> "$OUT/ab_$kv.err"; rc=$?
              echo "ab $kv rc=$rc $(python -c "import json,sys; d=json.load(open('$OUT/ab_$kv.json')); print(d['value'], d['ms_per_step'], d['parity_vs_cpu_sample'])" 2>/dev/null)"
              [ $rc -eq 0 ] || break
            done;;
@@ -85,7 +85,7 @@ for st in $STEPS; do
            rc=0
            for spec in "grid100:" "grid31:" "fabric100k:OSPF_SWEEP_NOTWIN=1,OSPF_SWEEP_NOTWINLV=1" "fabric100k-w:OSPF_SEED_NONH=1,OSPF_CLOSURE_NONH=1"; do
              T=${spec%%:*}; E=${spec#*:}; E=${E//,/ }; tag=${T}${E:+_ab}
-             timeout -k 10 420 env $E python bench.py --topology $T --steps 10 --warmup 2 --cpu-sample 8 > "$OUT/rec_$tag.json" 2> "$OUT/rec_$tag.err"; rc=$?
+             timeout -k 10 420 env $E python bench.py --full --topology $T --steps 10 --warmup 2 --cpu-sample 8 > "$OUT/rec_$tag.json" 2> "$OUT/rec_$tag.err"; rc=$?
              echo "record $tag rc=$rc $(head -c 300 "$OUT/rec_$tag.json")"
              [ $rc -eq 0 ] || break
            done;;
@@ -93,7 +93,7 @@ for st in $STEPS; do
            rc=0
            for spec in "wmulti:--mode wmulti" ${M1M_EXTRA:-}; do
              tag=${spec%%:*}; A=${spec#*:}; A=${A//,/ }
-             timeout -k 10 500 python bench.py --topology mesh1m --steps ${M1M_STEPS:-3} --warmup 1 --cpu-sample 4 $A > "$OUT/m1m_$tag.json" 2> "$OUT/m1m_$tag.err"; rc=$?
+             timeout -k 10 500 python bench.py --full --topology mesh1m --steps ${M1M_STEPS:-3} --warmup 1 --cpu-sample 4 $A > "$OUT/m1m_$tag.json" 2> "$OUT/m1m_$tag.err"; rc=$?
              echo "m1m $tag rc=$rc $(python -c "import json; d=json.load(open('$OUT/m1m_$tag.json')); print(d['value'], d['ms_per_step'], d['parity_vs_cpu_sample'])" 2>/dev/null)"
              [ $rc -eq 0 ] || break
            done;;

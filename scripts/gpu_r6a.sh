@@ -2,7 +2,7 @@
 # round 6: headline with the store probe + in-process leaf A/B (block order, chunk size)
 set -u
 OUT=gpurun_out/r6_${1:-a1}; mkdir -p $OUT; export TMPDIR=/tmp
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 \
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 \
   --ab "OSPF_LEAF_GROUP_MAJOR=1;OSPF_LEAF_CTILES=20;OSPF_LEAF_GROUP_MAJOR=1,OSPF_LEAF_CTILES=20;OSPF_LEAF_GROUP_MAJOR=1,OSPF_LEAF_CTILES=98" \
   > $OUT/bench.json 2> $OUT/bench.err || { tail -n 30 $OUT/bench.err; exit 1; }
 python - <<PY

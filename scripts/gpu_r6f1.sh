@@ -8,6 +8,6 @@ for v in base noprobe fulldepth; do
     noprobe) E=""; A="--no-probe";;
     fulldepth) E="OSPF_SWEEP_FULL_DEPTH=1"; A="";;
   esac
-  timeout -k 10 300 env $E python bench.py --cpu-sample 4 $A > $OUT/b_$v.json 2> $OUT/b_$v.err || { tail -20 $OUT/b_$v.err; exit 1; }
+  timeout -k 10 300 env $E python bench.py --full --cpu-sample 4 $A > $OUT/b_$v.json 2> $OUT/b_$v.err || { tail -20 $OUT/b_$v.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/b_$v.json')); print('$v', d['ms_per_step'], d['config']['root_classes']['first_sweep_after_graph_change'])"
 done

@@ -8,7 +8,7 @@ mkdir -p $O
 PORT=$((20000 + RANDOM % 20000))
 OPENR_BENCH_BACKEND=gloo OPENR_BENCH_SHARE_DEVICE=1 HSA_ENABLE_IPC_MODE_LEGACY=0 \
   timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-  --master-addr 127.0.0.1 --master-port $PORT bench.py --gpus $N --steps 1 --warmup 1 \
+  --master-addr 127.0.0.1 --master-port $PORT bench.py --full --gpus $N --steps 1 --warmup 1 \
   --topology $TOPO --roots 0 --dist-parity 64 --iso-reps 1 > $O/rehearse_${N}_${TOPO}.json 2> $O/rehearse_${N}_${TOPO}.err
 rc=$?
 python3 -c "

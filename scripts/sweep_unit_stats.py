@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-launch-unit kernel time and HBM traffic of an all-sources sweep from
-rocprofv3 output of `bench.py` (default sweep path).
+rocprofv3 output of `bench.py --full` (default sweep path).
 
-bench.py calls ospf_sweep_profile(reps) after the timed steps: every launch
+bench.py --full calls ospf_sweep_profile(reps) after the timed steps: every launch
 unit runs alone on its stream reps + 1 times, and the library queues one
 `sweep_unit_mark_kernel` dispatch before each unit and one after the last
 (openr_amd/csrc/engine/spf_sweep.hip). Dispatches between the k-th and the

@@ -41,7 +41,8 @@ def _launch_ranks(topology):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--topology", topology, "--roots", "0", "--dist-parity", "96", "--iso-reps", "1"]
+           "--topology", topology, "--roots", "0", "--full", "--dist-parity", "96",
+           "--iso-reps", "1"]
     return dict(proc=subprocess.Popen(cmd, stdout=out, stderr=err, cwd=ROOT, env=env),
                 out=out.name, err=err.name)
 

@@ -13,6 +13,7 @@
 
 #include "../../../include/openr_decision.h"
 #include "link_state.h"
+#include "../common/knobs.h"
 #include "spf_solver.h"
 #include "adjdb_thrift.h"
 
@@ -164,7 +165,7 @@ int odl_apply_hold(odl_ls* h, const oadj_stream* s, uint32_t first, uint32_t cou
           }
         }
       }, 256);
-      if (getenv("ODL_SPF_TIMING"))
+      if (knob_flag(Knob::ODL_SPF_TIMING))
         std::fprintf(stderr, "ODL_INGEST build_dbs_ms=%.1f\n",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
       const auto chs = h->ls.updateAdjacencyDatabases(dbs, hold_up_ttl, hold_down_ttl);
@@ -543,7 +544,7 @@ std::vector<std::optional<odl::RouteDb>> buildDbs(odl_ls* h, const std::vector<s
     odl::SpfSolver solver = areas ? odl::SpfSolver(*areas) : odl::SpfSolver(h->ls);
     const auto t0 = std::chrono::steady_clock::now();
     auto dbs = solver.buildRouteDbs(mes, prefixes, opt);
-    if (getenv("ODL_SPF_TIMING"))
+    if (knob_flag(Knob::ODL_SPF_TIMING))
       fprintf(stderr, "route_timing mes=%zu prefixes=%zu build_route_db_ms=%.3f\n", mes.size(),
               prefixes.size(),
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());

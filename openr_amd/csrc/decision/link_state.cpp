@@ -1,5 +1,6 @@
 // link_state.cpp — LinkState mirror (see link_state.h); SPF on the engine.
 #include "link_state.h"
+#include "../common/knobs.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -191,15 +192,15 @@ std::string Link::key() const {
 // ---------------------------------------------------------------- LinkState
 LinkState::LinkState(std::string area, int device)
     : area_(std::move(area)), device_(device), devices_{device} {
-  hostOnly_ = getenv("ODL_HOST_SPF") != nullptr;
-  degradeOnError_ = getenv("ODL_STRICT_ENGINE") == nullptr;
+  hostOnly_ = knob_flag(Knob::ODL_HOST_SPF);
+  degradeOnError_ = !knob_flag(Knob::ODL_STRICT_ENGINE);
 }
 
 LinkState::LinkState(std::string area, std::vector<int> devices)
     : area_(std::move(area)), device_(devices.empty() ? 0 : devices[0]), devices_(std::move(devices)) {
   if (devices_.empty()) throw std::invalid_argument("LinkState: no device");
-  hostOnly_ = getenv("ODL_HOST_SPF") != nullptr;
-  degradeOnError_ = getenv("ODL_STRICT_ENGINE") == nullptr;
+  hostOnly_ = knob_flag(Knob::ODL_HOST_SPF);
+  degradeOnError_ = !knob_flag(Knob::ODL_STRICT_ENGINE);
 }
 
 LinkState::~LinkState() {
@@ -404,7 +405,7 @@ LinkStateChange LinkState::updateAdjacencyDatabase(const AdjacencyDatabase& db, 
   // a topology change as in the reference (:751-754) -- in incremental mode
   // too (its kept-root rule covers metric / up / overload changes only)
   if (known && structural && snapVersion_ == version_ && keepsContract &&
-      !getenv("ODL_NO_LINK_PATCH")) {
+      !knob_flag(Knob::ODL_NO_LINK_PATCH)) {
     if (ch.topologyChanged || incremental_) {
       if (incremental_) incStats_.dropped += memoMetric_.size() + memoHops_.size();
       clearMemo();
@@ -434,7 +435,7 @@ LinkStateChange LinkState::updateAdjacencyDatabase(const AdjacencyDatabase& db, 
   // a node added while the snapshot is current: its (empty) row enters in
   // place, then the links it formed (peers that already advertised it)
   // patch their rows; the device graph reloads on its next use
-  if (!known && snapVersion_ == version_ && keepsContract && !getenv("ODL_NO_LINK_PATCH")) {
+  if (!known && snapVersion_ == version_ && keepsContract && !knob_flag(Knob::ODL_NO_LINK_PATCH)) {
     if (ch.topologyChanged) clearMemo();
     engineVersion_ = 0;
     const auto& nm = csr_->names;
@@ -469,7 +470,7 @@ std::vector<LinkStateChange> LinkState::updateAdjacencyDatabases(std::vector<Adj
   const uint32_t n = (uint32_t)dbs.size();
   std::vector<LinkStateChange> out(n);
   // (the bulk path makes links without holds)
-  bool bulk = n >= 64 && holdUpTtl == 0 && !getenv("ODL_NO_BULK_INGEST");
+  bool bulk = n >= 64 && holdUpTtl == 0 && !knob_flag(Knob::ODL_NO_BULK_INGEST);
   std::unordered_map<std::string, uint32_t> posOf;
   if (bulk) {
     posOf.reserve(n);
@@ -482,7 +483,7 @@ std::vector<LinkStateChange> LinkState::updateAdjacencyDatabases(std::vector<Adj
   }
 
   using Clock = std::chrono::steady_clock;
-  const bool timing = getenv("ODL_SPF_TIMING") != nullptr;
+  const bool timing = knob_flag(Knob::ODL_SPF_TIMING);
   Clock::time_point tp[6];
   tp[0] = Clock::now();
   std::vector<AdjacencyDatabase*> dbp(n);
@@ -601,7 +602,7 @@ LinkStateChange LinkState::deleteAdjacencyDatabase(const std::string& node) {
   // in place when the snapshot is current: the node's links leave their
   // rows (patchStructure), then its empty row leaves (ids above it move)
   const bool inPlace = snapVersion_ == version_ && !hostMetric_ && csr_->ids.count(node) &&
-                       !getenv("ODL_NO_LINK_PATCH");
+                       !knob_flag(Knob::ODL_NO_LINK_PATCH);
   std::vector<LinkPtr> removed;
   auto lm = linkMap_.find(node);
   if (lm != linkMap_.end()) {
@@ -642,7 +643,7 @@ LinkStateChange LinkState::deleteAdjacencyDatabase(const std::string& node) {
 // 4. rows are sorted by (neighbour id, rank) and written, then twins.
 const LinkState::Csr& LinkState::snapshot() {
   if (snapVersion_ == version_) return *csr_;
-  const bool tm = getenv("ODL_SNAP_TIMING") != nullptr;
+  const bool tm = knob_flag(Knob::ODL_SNAP_TIMING);
   auto t0 = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!tm) return;
@@ -905,7 +906,7 @@ void LinkState::prefetchKsp2(const std::string& src, const std::vector<std::stri
 
 void LinkState::startOpen(size_t nodes) {
   if (hostOnly_ || engine_ || opener_.joinable() || devices_.size() != 1 ||
-      getenv("ODL_NO_PREOPEN"))
+      knob_flag(Knob::ODL_NO_PREOPEN))
     return;
   // the warm-up: one link, one root (a warm-up graph as large as the
   // ingested one -- a hypercube, to size the batch path's buffers too -- cost
@@ -1001,7 +1002,7 @@ void LinkState::ensureEngine() {
     ++topoStats_.loads;
     engineVersion_ = snapVersion_;
   }
-  if ((opening || loading) && getenv("ODL_SPF_TIMING"))
+  if ((opening || loading) && knob_flag(Knob::ODL_SPF_TIMING))
     fprintf(stderr, "ensure_engine open=%d load=%d open_ms=%.3f load_ms=%.3f\n", opening, loading,
             std::chrono::duration<double, std::milli>(tOpen - t0).count(),
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tOpen).count());
@@ -1406,7 +1407,7 @@ void LinkState::prefetchSpfImpl(const std::vector<std::string>& roots, bool useL
         rows->nbrs = nbrsOf(part[i]);
         memo.emplace(csr_->names[part[i]], SpfResult(std::move(rows)));
       }
-      if (getenv("ODL_SPF_TIMING")) {
+      if (knob_flag(Knob::ODL_SPF_TIMING)) {
         const auto t2 = std::chrono::steady_clock::now();
         fprintf(stderr, "spf_timing roots=%zu W=%u engine_ms=%.3f build_result_ms=%.3f\n",
                 part.size(), W, std::chrono::duration<double, std::milli>(t1 - t0).count(),
@@ -1610,7 +1611,7 @@ void LinkState::prefetchKsp2Impl(const std::string& src, const std::vector<std::
   // on the engine; records hold link ids. A destination over the engine's
   // budgets is computed by the host path below (same results, slower).
   uint32_t kCap = 1024;  // record words per destination and k
-  if (const char* x = getenv("ODL_KSP_CAP")) kCap = std::max(2, std::min(2048, atoi(x)));
+  kCap = (uint32_t)knob_int(Knob::ODL_KSP_CAP, (int)kCap);
   const size_t n = ids.size();
   std::vector<uint32_t> k1(n * kCap), k2(n * kCap), status(n);
   auto runOn = [&](ospf_ctx* c, size_t a0, size_t a1) {

@@ -241,7 +241,7 @@ std::vector<NextHop> SpfSolver::ksp2Paths(size_t ai, const std::string& me,
 
 std::optional<UnicastRoute> SpfSolver::prefixRoute(const std::string& me, const PrefixRoute& pr,
                                                    const RouteOptions& opt) {
-  const bool tm = getenv("ODL_ROUTE_TIMING") != nullptr;
+  const bool tm = knob_flag(Knob::ODL_ROUTE_TIMING);
   auto tl = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!tm) return;
@@ -470,7 +470,7 @@ std::optional<RouteDb> SpfSolver::buildRouteDb(const std::string& me,
   // entry runs getKthPaths, which fills a memo, so those are built on this
   // thread. The results are looked up (and memoised) here, on the calling
   // thread; the host threads below only read them
-  const bool tm = getenv("ODL_ROUTE_TIMING") != nullptr;
+  const bool tm = knob_flag(Knob::ODL_ROUTE_TIMING);
   auto tl = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!tm) return;

@@ -25,6 +25,8 @@
 
 #include <unistd.h>
 
+#include "../common/knobs.h"
+
 namespace host_pool {
 
 class Pool {
@@ -86,7 +88,7 @@ class Pool {
  private:
   Pool() : pid_(getpid()) {
     uint32_t hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    if (const char* e = std::getenv("OPENR_HOST_THREADS")) hw = (uint32_t)std::max(1, std::atoi(e));
+    hw = (uint32_t)knob_int(Knob::OPENR_HOST_THREADS, (int)hw);
     for (uint32_t i = 0; i + 1 < hw; ++i) {
       try {
         workers_.emplace_back([this, i] { loop(i); });

@@ -702,164 +702,6 @@ __device__ __forceinline__ void write_row_nhw(const DevGraph& g, const CoverGrap
   }
 }
 
-// Expansion of queued nodes each from its own current distance, for the
-// delta-stepping variant: a relaxation that lowers a distance (LDS atomicMin)
-// sets the node's dirty bit and the round's flag.
-__device__ __forceinline__ void expand_bf(const CoverGraph& C, uint32_t* s_D, uint32_t* nxt,
-                                          const uint32_t* q, uint32_t cnt, uint32_t* s_pre,
-                                          uint32_t* s_any, uint32_t lane) {
-  for (uint32_t b0 = 0; b0 < cnt; b0 += kWave) {
-    const uint32_t j = b0 + lane;
-    uint32_t beg = 0, deg = 0, du = kInf;
-    if (j < cnt) {
-      const uint32_t u = q[j];
-      beg = C.crow[u];
-      deg = C.crow[u + 1] - beg;
-      du = s_D[u];
-    }
-    uint32_t inc = deg;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const uint32_t y = (uint32_t)__shfl_up((int)inc, o, kWave);
-      if (lane >= (uint32_t)o) inc += y;
-    }
-    s_pre[lane] = inc;
-    s_pre[kWave + lane] = beg;
-    s_pre[2 * kWave + lane] = du;
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t total = (uint32_t)__shfl((int)inc, kWave - 1, kWave);
-    constexpr uint32_t kU = 16;
-    bool any = false;
-    for (uint32_t f0 = 0; f0 < total; f0 += kWave * kU) {
-      uint2 ed[kU];
-      uint32_t base[kU];
-#pragma unroll
-      for (uint32_t u = 0; u < kU; ++u) {
-        const uint32_t f = f0 + u * kWave + lane;
-        ed[u] = make_uint2(0u, kInf);
-        base[u] = kInf;
-        if (f < total) {
-          uint32_t lo = 0, hi = kWave - 1;  // first k with pre[k] > f
-#pragma unroll
-          for (int it = 0; it < 6; ++it) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (s_pre[mid] > f) hi = mid;
-            else lo = mid + 1;
-          }
-          const uint32_t before = lo ? s_pre[lo - 1] : 0u;
-          ed[u] = C.cedge[s_pre[kWave + lo] + (f - before)];
-          base[u] = s_pre[2 * kWave + lo];
-        }
-      }
-#pragma unroll
-      for (uint32_t u = 0; u < kU; ++u) {
-        if (ed[u].y == kInf || base[u] == kInf) continue;
-        const uint32_t nd = base[u] + ed[u].y;
-        const uint32_t v = ed[u].x;
-        if (nd < atomicMin(&s_D[v], nd)) {
-          atomicOr(&nxt[v >> 5], 1u << (v & 31u));
-          any = true;
-        }
-      }
-    }
-    if (__ballot(any) && lane == 0) *s_any = 1u;
-    __builtin_amdgcn_wave_barrier();  // s_pre is rewritten by the next pass
-  }
-}
-
-// Delta-stepping over the contracted graph (OSPF_COVER_DELTA=d; not the
-// default): the distance axis in buckets of width d; a bucket's round
-// expands the "dirty" transit cover nodes (distance lowered since their last
-// expansion) whose distance lies below the bucket's end, and repeats until
-// none is left there; the next bucket starts at the smallest dirty distance.
-// Exact at the fixed point (metrics >= 1), and a round scans the dirty bitmap
-// (nS / 32 words) instead of the distances. Measured on F100k-w: 162 / 257 /
-// 318 ms at d = 8 / 32 / 64 against 82 ms for the Dial rounds (and 341 ms for
-// plain frontier Bellman-Ford): every re-expansion of a spine relaxes all its
-// 1,781 edges again; a light / heavy edge split would be the next step.
-__global__ void __launch_bounds__(512) cover_delta_kernel(DevGraph g, CoverGraph C, CoverArgs a,
-                                                          uint32_t delta) {
-  extern __shared__ uint32_t s_D[];  // [nS] distances, [nw] transit bits, [nw] dirty bits
-  __shared__ uint32_t s_q[kWaves][kQ];
-  __shared__ uint32_t s_pre[kWaves][3 * kWave];
-  __shared__ uint32_t s_any[2], s_min;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-  const uint32_t nS = C.nS, V = g.V, nw = (nS + 31u) / 32u;
-  uint32_t* s_tr = s_D + nS;
-  uint32_t* s_dirty = s_tr + nw;
-  for (uint32_t x = tid; x < nw; x += kBlock) s_tr[x] = C.ctr[x];
-  for (uint32_t i = blockIdx.x; i < a.n; i += gridDim.x) {
-    const uint32_t rn = a.roots[i];
-    const uint32_t r = rn < V ? C.cix[rn] : kInf;
-    if (r >= nS) {  // not a cover node (or a bad id): its row is left alone
-      if (tid == 0) atomicOr(a.err, 64u);
-      continue;
-    }
-    for (uint32_t x = tid; x < nS; x += kBlock) s_D[x] = x == r ? 0u : kInf;
-    for (uint32_t x = tid; x < nw; x += kBlock) s_dirty[x] = x == (r >> 5) ? 1u << (r & 31u) : 0u;
-    if (tid == 0) {
-      s_any[0] = s_any[1] = 0u;
-      s_min = kInf;
-    }
-    __syncthreads();
-    uint32_t hi = delta, par = 0;
-    while (true) {
-      uint32_t* q = s_q[wave];
-      uint32_t cnt = 0, m2 = kInf;
-      bool popped = false;
-      for (uint32_t w0 = wave * kWave; w0 < nw; w0 += kBlock) {
-        const uint32_t w = w0 + lane;
-        uint32_t bits = w < nw ? s_dirty[w] : 0u, take = 0u;
-        for (uint32_t b = bits; b; b &= b - 1u) {
-          const uint32_t u = 32u * w + (uint32_t)__builtin_ctz(b);
-          const uint32_t d = s_D[u];
-          if (d < hi) take |= b & (0u - b);
-          else m2 = min(m2, d);
-        }
-        if (take) {
-          atomicAnd(&s_dirty[w], ~take);  // a later improvement sets the bit again
-          popped = true;
-          take &= s_tr[w] | (w == (r >> 5) ? 1u << (r & 31u) : 0u);  // transit or the root
-        }
-        while (__ballot(take != 0u)) {
-          const bool has = take != 0u;
-          const uint32_t u = has ? 32u * w + (uint32_t)__builtin_ctz(take) : 0u;
-          if (has) take &= take - 1u;
-          const uint64_t bal = __ballot(has);
-          if (has) q[cnt + __popcll(bal & ((1ull << lane) - 1ull))] = u;
-          cnt += (uint32_t)__popcll(bal);
-          if (cnt > kQ - kWave) {
-            __builtin_amdgcn_wave_barrier();
-            expand_bf(C, s_D, s_dirty, q, cnt, s_pre[wave], &s_any[par], lane);
-            cnt = 0;
-          }
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (cnt) expand_bf(C, s_D, s_dirty, q, cnt, s_pre[wave], &s_any[par], lane);
-      if (__ballot(popped) && lane == 0) s_any[par] = 1u;
-      m2 = wave_min32(m2);
-      if (lane == 0 && m2 != kInf) atomicMin(&s_min, m2);
-      __syncthreads();
-      const bool again = s_any[par] != 0u;
-      const uint32_t nxt = s_min;
-      __syncthreads();  // every thread has read the flags
-      if (tid == 0) {
-        s_any[par] = 0u;
-        s_min = kInf;
-      }
-      par ^= 1u;
-      if (!again) {  // the bucket below hi is settled: on to the next dirty distance
-        if (nxt == kInf) break;
-        hi = nxt + delta;
-      }
-      __syncthreads();  // the flag resets are visible before their use
-    }
-    write_row(g, C, a.dist + (size_t)i * V, s_D, s_tr, r, tid, kBlock);
-    __syncthreads();  // s_D is reused by the next root
-  }
-}
-
 // Closure rows by node tiles: block = (chunk of kLtTiles node tiles, chunk of
 // kLtRoots roots). A tile is <= 256 consecutive nodes whose own cover indices
 // (cover nodes) and in-links' cover indices (leaves) form a union U of <= 256
@@ -1384,22 +1226,8 @@ hipError_t launch_cover_spf(const DevGraph& g, const CoverGraph& C, const CoverA
   if (a.nhload && (!a.dload || !a.nh || a.NW == 0 || a.NW > kClMaxNW)) return hipErrorInvalidValue;
   if (a.nhpos && (a.dload || !a.nhm || !a.nh || a.NW == 0 || a.NW > kSeedMaxNW))
     return hipErrorInvalidValue;
-  const char* e = getenv("OSPF_COVER_DELTA");
-  if (e && !a.rowpos && !a.dcomp && !a.dload) {  // delta-stepping (experiment)
-    const uint32_t delta = (uint32_t)std::max(1, atoi(e));
-    const size_t lds = ((size_t)C.nS + 2u * ((C.nS + 31u) / 32u)) * 4u;
-    const uint32_t per_cu = std::max<uint32_t>(1, (uint32_t)((150u * 1024u) / (lds + 12u * 1024u)));
-    const uint32_t grid = std::min<uint32_t>(a.n, n_cu * std::min<uint32_t>(per_cu, 4u));
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)cover_delta_kernel,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(cover_delta_kernel, dim3(grid), dim3(kBlock), lds, s, g, C, a, delta);
-    return hipGetLastError();
-  }
   const size_t lds = ((size_t)C.nS + (C.nS + 31u) / 32u) * 4u;
-  if (a.nhload && !getenv("OSPF_COVER_ROWS_IN_DIAL")) {  // closure rows with next hops
+  if (a.nhload && !knob_flag(Knob::OSPF_COVER_ROWS_IN_DIAL)) {  // closure rows with next hops
     const uint32_t grid = std::min<uint32_t>(a.n, n_cu * 2u);
     const size_t lds = ((size_t)C.nS + 1u + (C.nS + 31u) / 32u) * 4u;  // + the padding slot
     auto go = [&](const void* k) -> hipError_t {

@@ -155,8 +155,8 @@ Plan make_plan(const ospf_ctx* c, uint32_t W, uint32_t ign_cap, bool unit, uint3
   }
   // test/benchmark knob: OSPF_FORCE_VARIANT=0..4 forces a kernel variant when
   // its state fits (e.g. the HBM-state Dial kernel on a small graph).
-  if (const char* f = getenv("OSPF_FORCE_VARIANT")) {
-    const int want = atoi(f);
+  if (knob_set(Knob::OSPF_FORCE_VARIANT)) {
+    const int want = knob_int(Knob::OSPF_FORCE_VARIANT);
     if (want >= 0 && want <= 7 && fits(want)) p.variant = want;
   }
   const size_t ldsz[8] = {full, half, head, bfs_nh, bfs, 0, head, 0};
@@ -167,10 +167,6 @@ Plan make_plan(const ospf_ctx* c, uint32_t W, uint32_t ign_cap, bool unit, uint3
     p.block = p.lds > 80 * 1024 ? 1024 : (V >= 4096 ? 512 : 256);
   else
     p.block = V >= 4096 ? 512 : 256;
-  if (const char* b = getenv("OSPF_BLOCK")) {  // experiment knob: 256/512/1024
-    const int want = atoi(b);
-    if (want == 256 || want == 512 || want == 1024) p.block = (uint32_t)want;
-  }
   return p;
 }
 
@@ -264,10 +260,10 @@ int run_msbfs(ospf_ctx* c, const ospf_batch* b, hipStream_t s) {
   // written once, whole, by msbfs_rows (needs depth + 2 <= 255: the check
   // level past the bound is recorded too), which also folds
   // the digest in (no row re-read, no row scratch); packed planes need it
-  const bool defer = c->depth_bound <= 253 && !getenv("OSPF_MS_NODEFER");
-  MsShape sh = ms_shape(b->n_roots, kcap, defer && getenv("OSPF_MS_PACK"));
-  if (const char* e = getenv("OSPF_MS_R")) {  // test knob: force R (packs when defer)
-    const uint32_t R = std::min(64, std::max(1, atoi(e)));
+  const bool defer = c->depth_bound <= 253 && !knob_flag(Knob::OSPF_MS_NODEFER);
+  MsShape sh = ms_shape(b->n_roots, kcap, defer && knob_flag(Knob::OSPF_MS_PACK));
+  if (knob_set(Knob::OSPF_MS_R)) {  // test knob: force R (packs when defer)
+    const uint32_t R = (uint32_t)knob_int(Knob::OSPF_MS_R);
     if (defer && kcap > 32) {
       sh.R = R;
       sh.PP = sh.OW = 64 / R;
@@ -288,10 +284,9 @@ int run_msbfs(ospf_ctx* c, const ospf_batch* b, hipStream_t s) {
   // seen, accb, 2 frontier records (16 B), planes (u64 per node each) + lev
   // (64 B per node) + found, mass
   const size_t per_vb = align_up((size_t)V * 8ull * (6 + kp) + (defer ? V * 64ull : 0) + lmax * 8ull, 256);
-  uint32_t push_div = 8;  // push a level when its frontier's edge mass * push_div < E
-  if (const char* e = getenv("OSPF_MS_PUSH_DIV")) push_div = (uint32_t)std::max(0, atoi(e));
-  uint32_t nb_cap = 96;
-  if (const char* e = getenv("OSPF_MS_NB")) nb_cap = std::max(1, atoi(e));
+  // push a level when its frontier's edge mass * push_div < E
+  const uint32_t push_div = (uint32_t)knob_int(Knob::OSPF_MS_PUSH_DIV, 8);
+  uint32_t nb_cap = (uint32_t)knob_int(Knob::OSPF_MS_NB);
   nb_cap = (uint32_t)std::max<size_t>(1, std::min<size_t>(nb_cap, (6ull << 30) / per_vb));
   // roots per chunk: bounded when digest rows live in scratch
   const size_t row_bytes = (dist_scr ? V * 4ull : 0) + (nh_scr ? (size_t)V * W * 4ull : 0);
@@ -305,8 +300,8 @@ int run_msbfs(ospf_ctx* c, const ospf_batch* b, hipStream_t s) {
   // W = 3 slower (11.1 -> 12.2 ms: the rows kernel there is not store-bound and
   // the extra pass costs 1.3 ms), hence the threshold. OSPF_MS_ILV=0/1 forces.
   bool ilv = defer && W >= 8 && W <= 64 && (flags & OSPF_WANT_NH) && !nh_scr;
-  if (const char* e = getenv("OSPF_MS_ILV"))
-    ilv = atoi(e) && defer && W > 1 && W <= 64 && (flags & OSPF_WANT_NH) && !nh_scr;
+  if (knob_set(Knob::OSPF_MS_ILV))
+    ilv = knob_flag(Knob::OSPF_MS_ILV) && defer && W > 1 && W <= 64 && (flags & OSPF_WANT_NH) && !nh_scr;
   if (ilv) {
     const size_t cap = 8ull << 30, per_root = (size_t)V * W * 4ull;
     if ((size_t)chunk * per_root > cap)
@@ -315,7 +310,7 @@ int run_msbfs(ospf_ctx* c, const ospf_batch* b, hipStream_t s) {
   // merged rows (2..7 words, one per pass): every pass of a batch in the same
   // round, all of a batch's passes on one XCD (nb a multiple of 8 * npass)
   bool merged = defer && !ilv && npass > 1 && sh.PP == 1 && sh.OW == 1 && W <= 7 &&
-                (flags & (OSPF_WANT_NH | OSPF_WANT_DIGEST)) && !getenv("OSPF_MS_NOMERGE");
+                (flags & (OSPF_WANT_NH | OSPF_WANT_DIGEST)) && !knob_flag(Knob::OSPF_MS_NOMERGE);
   uint32_t nb_max =
       std::min<uint32_t>(nb_cap, ((std::min(chunk, b->n_roots) + sh.R - 1) / sh.R) * npass);
   if (merged) {
@@ -407,8 +402,8 @@ int run_wdial(ospf_ctx* c, const ospf_batch* b, bool hop, hipStream_t s) {
     NB = ospf::kWDialMaxNB;
     delta = (maxw + NB - 2) / (NB - 1);
   }
-  if (const char* e = getenv("OSPF_WD_DELTA")) {  // test knob: force tagged buckets
-    const uint32_t dl = (uint32_t)std::max(1, atoi(e));
+  {  // test knob: force tagged buckets
+    const uint32_t dl = (uint32_t)knob_int(Knob::OSPF_WD_DELTA);
     if (dl > 1) {
       delta = std::max(delta, dl);
       NB = std::min<uint32_t>(ospf::kWDialMaxNB, (maxw + delta - 1) / delta + 1);
@@ -424,25 +419,23 @@ int run_wdial(ospf_ctx* c, const ospf_batch* b, bool hop, hipStream_t s) {
   // fewer roots than groups: wider groups (more lanes per round) until every
   // group has a root
   while (G < 16 && n < (uint64_t)c->n_cu * (16 / G)) G *= 2;
-  if (const char* e = getenv("OSPF_WD_GROUP")) G = (uint32_t)std::max(1, std::min(16, atoi(e)));
+  G = (uint32_t)knob_int(Knob::OSPF_WD_GROUP, (int)G);
   while (16 % G) --G;
   uint32_t ngroups =
       std::max<uint32_t>(1, std::min<uint32_t>(n, (uint32_t)c->n_cu * (16 / G)));
   // knob: fewer roots in flight (their frontiers' state lines stay cached)
-  if (const char* e = getenv("OSPF_WD_NGROUPS"))
-    ngroups = std::max<uint32_t>(1, std::min<uint32_t>(ngroups, (uint32_t)atoi(e)));
-  size_t budget = 4096ull << 20;
-  if (const char* e = getenv("OSPF_WD_LIST_MB")) budget = (size_t)std::max(1, atoi(e)) << 20;
+  ngroups = std::min(ngroups, (uint32_t)knob_int(Knob::OSPF_WD_NGROUPS, (int)ngroups));
+  const size_t budget = (size_t)knob_int(Knob::OSPF_WD_LIST_MB) << 20;
   const size_t eb = delta > 1 ? 8 : 4;
   uint64_t bcap = budget / ((uint64_t)ngroups * NB * eb);
   bcap = std::max<uint64_t>(64, std::min<uint64_t>(bcap, V));
-  if (const char* e = getenv("OSPF_WD_BCAP")) bcap = (uint64_t)std::max(1, atoi(e));  // test knob
+  if (knob_set(Knob::OSPF_WD_BCAP)) bcap = (uint64_t)knob_int(Knob::OSPF_WD_BCAP);  // test knob
   // packed state (spf_wdial.hip PACK): one word per node for roots with at
   // most 16 distinct neighbours (the caller's max_root_neighbors hint)
   const uint32_t kcap = b->max_root_neighbors ? b->max_root_neighbors : 32u * W;
   uint32_t pk_bits = (W == 1 && kcap <= 16) ? (kcap <= 8 ? 8u : 16u) : 0u;
-  if (const char* e = getenv("OSPF_WD_PACK")) {  // knob: 0 = off, 8 / 16 = field width
-    const int v = atoi(e);
+  if (knob_set(Knob::OSPF_WD_PACK)) {  // knob: 0 = off, 8 / 16 = field width
+    const int v = knob_int(Knob::OSPF_WD_PACK);
     pk_bits = (v == 0 || W != 1 || kcap > (uint32_t)v || (v != 8 && v != 16)) ? 0u : (uint32_t)v;
   }
   const bool want_dist = b->flags & OSPF_WANT_DIST, want_nh = b->flags & OSPF_WANT_NH;
@@ -472,7 +465,7 @@ int run_wdial(ospf_ctx* c, const ospf_batch* b, bool hop, hipStream_t s) {
   a.ngroups = ngroups;
   a.pk_bits = pk_bits;
   a.pk = pk_bits ? (uint32_t*)(sp + sz_lists + sz_dist + sz_nh) : nullptr;
-  a.wg_scope = getenv("OSPF_WD_WGSCOPE") ? 1u : 0u;
+  a.wg_scope = knob_flag(Knob::OSPF_WD_WGSCOPE) ? 1u : 0u;
   HIPCHK(c, hipSetDevice(c->device));
   hipError_t e = ospf::launch_wdial(c->g, a, s);
   if (e != hipSuccess) return hip_fail(c, e, "launch_wdial");
@@ -495,7 +488,7 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
   const bool unit = c->info.unit_metric != 0;
   const uint32_t nn = c->h_dn_off[src + 1] - c->h_dn_off[src];
   const uint32_t W = std::max<uint32_t>(1, (nn + 31) / 32);
-  const bool ms = unit && c->g.n_lid && c->depth_bound <= 253 && !getenv("OSPF_KSP_ROWS");
+  const bool ms = unit && c->g.n_lid && c->depth_bound <= 253 && !knob_flag(Knob::OSPF_KSP_ROWS);
   constexpr uint32_t lmax = 256;
   const uint32_t dw = (V + 31) / 32;
   const size_t sz_ign = align_up((size_t)n * cap * 4ull, 256), sz_cnt = align_up(n * 4ull, 256),
@@ -507,14 +500,13 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
   const size_t st_zero = (size_t)V * 8ull * 6 + lmax * 8ull + igw * 4ull;
   const size_t per_vb = align_up(st_zero, 256) + align_up((size_t)c->g.E * 8ull, 256);
   const size_t per_vb_slot = (size_t)V * 64ull + 64ull * dw * 4ull;
-  uint32_t nb_cap = 96;
-  if (const char* e = getenv("OSPF_MS_NB")) nb_cap = std::max(1, atoi(e));
+  uint32_t nb_cap = (uint32_t)knob_int(Knob::OSPF_MS_NB);
   nb_cap = (uint32_t)std::max<size_t>(1, std::min<size_t>(nb_cap, (6ull << 30) / (per_vb + per_vb_slot)));
   const uint32_t total_vb = (n + 63) / 64, nb_max = std::min(nb_cap, total_vb);
   const uint32_t rounds = (total_vb + nb_max - 1) / nb_max;
   uint32_t slots = (uint32_t)std::max<size_t>(
       1, std::min<size_t>({(size_t)16, (size_t)rounds, (12ull << 30) / (per_vb_slot * nb_max)}));
-  if (const char* e = getenv("OSPF_KSP_SLOTS")) slots = std::max(1, std::min((int)slots, atoi(e)));
+  slots = std::min(slots, (uint32_t)knob_int(Knob::OSPF_KSP_SLOTS, (int)slots));
   const size_t sz_lev = align_up((size_t)nb_max * V * 64ull, 256),
                sz_sdead = align_up((size_t)nb_max * 64ull * dw * 4ull, 256) +
                           align_up((nb_max * 64ull + 2) * 4ull, 256);
@@ -567,12 +559,9 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
   t.dead = d_dead;
   t.dead_words = dw;
   // unit metric: runs past kTraceBudget DFS steps finish on the 16-wave kernel
-  constexpr uint32_t kTraceBudget = 256;
-  t.budget = unit && !getenv("OSPF_KSP_NOHEAVY") ? kTraceBudget : 0u;
-  if (const char* x = getenv("OSPF_KSP_BUDGET"))  // test knob: send runs to the heavy kernel
-    if (t.budget) t.budget = (uint32_t)std::max(1, atoi(x));
-  t.look = 16;  // (OSPF_KSP_LOOK: A/B knob, 0 = no lookahead)
-  if (const char* x = getenv("OSPF_KSP_LOOK")) t.look = (uint32_t)std::max(0, atoi(x));
+  // (OSPF_KSP_BUDGET, 256 steps; a small value sends runs to the heavy kernel)
+  t.budget = unit && !knob_flag(Knob::OSPF_KSP_NOHEAVY) ? (uint32_t)knob_int(Knob::OSPF_KSP_BUDGET) : 0u;
+  t.look = (uint32_t)knob_int(Knob::OSPF_KSP_LOOK);  // (A/B knob, 0 = no lookahead)
   t.heavy = (uint32_t*)((char*)d_dead + align_up((size_t)tchunk * dw * 4ull, 256));
   t.heavy_ctr = t.heavy + tchunk;
   hipError_t e = hipSuccess;
@@ -597,14 +586,10 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
   // the stream of the full reruns: the caller's, or a high-priority one
   // while the decremental kernels run beside them (run_ksp2's presplit)
   hipStream_t fs = s;
-  // after_first: called once the first round's traversal is done on fs (the
-  // host waits for it anyway): the presplit runs' first round gets the GPU
-  // alone, the decremental kernels are launched beside the later rounds
   // before_last(R_n): called once before the last round is queued; it may
   // append runs to the R_* arrays (their capacity) and raise R_n
   auto full_reruns = [&](const uint32_t* R_dsts, uint32_t R_n, const uint32_t* R_ign,
                          const uint32_t* R_cnt, uint32_t* R_status, uint32_t* R_k2,
-                         const std::function<int()>& after_first = nullptr,
                          const std::function<int(uint32_t&)>& before_last = nullptr) -> int {
     ospf::TraceArgs t = t_k1;
     uint32_t total_vb = (R_n + 63) / 64;  // this set's virtual batches (<= the carve'fs)
@@ -645,8 +630,7 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
         a.nb = std::min(nb_max, total_vb - vb0);
         a.lmax = lmax;
         a.kcap = nn;
-        a.push_div = 8;
-        if (const char* x = getenv("OSPF_MS_PUSH_DIV")) a.push_div = (uint32_t)std::max(0, atoi(x));
+        a.push_div = (uint32_t)knob_int(Knob::OSPF_MS_PUSH_DIV, 8);
         a.defer = 1;
         a.err = c->d_err;
         a.front = (uint64_t*)st;
@@ -660,9 +644,7 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
         const size_t zero = (char*)(a.igb + (size_t)a.nb * igw) - st;
         a.igm = (uint64_t*)(st + align_up(zero, 256));
         a.lev = lev;
-        // a batch stops once all its destinations are reached
-        // (OSPF_KSP_FULL_DEPTH: every level, as before)
-        a.kdst = getenv("OSPF_KSP_FULL_DEPTH") ? nullptr : R_dsts;
+        a.kdst = R_dsts;  // a batch stops once all its destinations are reached
         HIPCHK(c, ospf::zero_async(st, zero, fs));
         if (r >= slots) HIPCHK(c, hipStreamWaitEvent(fs, ev_tr[slot], 0));  // slot's trace done
         HIPCHK(c, ospf::zero_async(lev, (size_t)a.nb * V * 64ull, fs));
@@ -670,7 +652,7 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
         if (e != hipSuccess) return hip_fail(c, e, "launch_ksp_masks");
         uint32_t d = std::max<uint32_t>(2, c->depth_bound);
         // test knob: start with fewer levels (exercises the continuation below)
-        if (const char* x = getenv("OSPF_KSP_D0")) d = std::max(2, std::min((int)d, atoi(x)));
+        d = std::min(d, (uint32_t)knob_int(Knob::OSPF_KSP_D0, (int)d));
         e = ospf::launch_msbfs_ksp(c->g, a, 1, d, fs);
         if (e != hipSuccess) return hip_fail(c, e, "launch_msbfs_ksp");
         // masked runs may be deeper than the graph's bound: continue while any
@@ -699,10 +681,6 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
         }
         HIPCHK(c, hipEventRecord(ev_bfs[slot], fs));
         HIPCHK(c, hipStreamWaitEvent(c->aux, ev_bfs[slot], 0));
-        if (r == 0 && after_first) {
-          const int rc3 = after_first();
-          if (rc3) return rc3;
-        }
         const uint32_t r0 = vb0 * 64u;
         ospf::TraceArgs t2 = t;
         t2.dsts = R_dsts + r0;
@@ -767,7 +745,7 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
     }
     return OSPF_OK;
   };
-  if (getenv("OSPF_KSP_NODECR")) return full_reruns(k->dsts, n, d_ign, d_cnt, k->status, k->k2);
+  if (knob_flag(Knob::OSPF_KSP_NODECR)) return full_reruns(k->dsts, n, d_ign, d_cnt, k->status, k->k2);
   // decremental reruns (spf_ksp2.hip): the source's row + per-run lost
   // supports. Runs whose ignore list is past its budget are known before it
   // starts (presplit): their full reruns go on `s` while the decremental
@@ -775,17 +753,13 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
   {
     const size_t dwb = align_up((size_t)dw * 4ull, 256);
     uint32_t bpc = ospf::ksp_decr_blocks_per_cu();
-    if (const char* x = getenv("OSPF_KSP_DECR_BPC")) bpc = std::max(1u, std::min(bpc, (uint32_t)atoi(x)));
-    // (OSPF_KSP_DECR_R: runs per block instead of persistent blocks)
-    uint32_t decr_r = 0;
-    if (const char* x = getenv("OSPF_KSP_DECR_R")) decr_r = (uint32_t)std::max(0, atoi(x));
-    const uint32_t nblk = decr_r ? std::max(1u, (n + decr_r - 1) / decr_r)
-                                 : std::max<uint32_t>(1, bpc * (uint32_t)c->n_cu);
+    bpc = std::min(bpc, (uint32_t)knob_int(Knob::OSPF_KSP_DECR_BPC, (int)bpc));
+    const uint32_t nblk = std::max<uint32_t>(1, bpc * (uint32_t)c->n_cu);  // persistent blocks
     const uint32_t hblk = 2u * (uint32_t)c->n_cu;  // ksp_decr_heavy_kernel: 2 per CU
     const size_t sz_tc = align_up(V * 4ull, 256), sz_fb = align_up(n * 4ull, 256), sz_ctr = 256,
                  sz_dd = dwb * std::max(nblk, hblk);
     // heavy runs' pruning (unit metric): level order + per-block good bits
-    const bool prune = t_k1.budget && !getenv("OSPF_KSP_NOPRUNE");
+    const bool prune = t_k1.budget && !knob_flag(Knob::OSPF_KSP_NOPRUNE);
     const size_t sz_ord = prune ? align_up(V * 4ull, 256) + align_up(2 * 257 * 4ull, 256) : 0,
                  sz_good = prune ? dwb * hblk + (size_t)hblk * ospf::kGoodBig * 4ull : 0;
     const size_t sz_pb = align_up((n + 31) / 32 * 4ull, 256);
@@ -819,13 +793,6 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
     td.heavy = d_hq;
     td.heavy_ctr = d_ctr + 4;
     td.err = c->d_err;
-    td.decr_runs = decr_r;
-    // a run past the map budget goes to the full reruns (with presplit runs
-    // it joins their last round) instead of the 16-wave kernel, whose
-    // single slow run (F100k: 10.8 ms) had ended the launch: 20.17 -> 20.04
-    // ms (profiles/r06/h1_ksp2_order_ab.txt; OSPF_KSP_MAP_FB=0 restores it)
-    td.map_fb = 1u;
-    if (const char* x = getenv("OSPF_KSP_MAP_FB")) td.map_fb = atoi(x) ? 1u : 0u;
     if (prune) {
       char* q = dp + sz_tc + 3 * sz_fb + sz_ctr + sz_dd;
       uint32_t* d_ord = (uint32_t*)q;
@@ -840,10 +807,9 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
     }
     // (presplit count in ctr[12])
     uint32_t npre = 0;
-    const bool split = getenv("OSPF_KSP_NOSPLIT") == nullptr;
+    const bool split = !knob_flag(Knob::OSPF_KSP_NOSPLIT);
     if (split) {
-      td.src_cut = 16;  // (OSPF_KSP_SRCCUT: A/B knob, 0 = off)
-      if (const char* x = getenv("OSPF_KSP_SRCCUT")) td.src_cut = (uint32_t)std::max(0, atoi(x));
+      td.src_cut = (uint32_t)knob_int(Knob::OSPF_KSP_SRCCUT);  // (A/B knob, 0 = off)
       td.pre_bits = (uint32_t*)(dp + sz_tc + 3 * sz_fb + sz_ctr + sz_dd + sz_ord + sz_good);
       HIPCHK(c, ospf::zero_async(td.pre_bits, (n + 31) / 32 * 4ull, s));
       e = ospf::launch_ksp_presplit(c->g, td, d_pre, d_ctr + 12, s);
@@ -855,7 +821,7 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
     // with presplit runs: the decremental kernels on a low-priority stream,
     // the full reruns (the launch's critical path) on a high-priority one
     // (OSPF_KSP_NOPRIO: the caller's stream for them)
-    const bool prio = getenv("OSPF_KSP_NOPRIO") == nullptr;
+    const bool prio = !knob_flag(Knob::OSPF_KSP_NOPRIO);
     if (npre) {
       if (!c->ksp_aux || !c->ksp_hi) {
         int lo = 0, hi = 0;
@@ -875,37 +841,28 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
     }
     // OSPF_KSP_DEBUG=2: a log of the heavy runs (run, start, traced, end)
     unsigned long long* d_hlog = nullptr;
-    const char* kdbg = getenv("OSPF_KSP_DEBUG");
-    if (kdbg && atoi(kdbg) >= 2 && td.budget) {
+    if (knob_int(Knob::OSPF_KSP_DEBUG) >= 2 && td.budget) {
       HIPCHK(c, dev_malloc(c, (void**)&d_hlog, 4ull * 65536 * 8));
       td.hlog = d_hlog;
     }
     // the decremental kernels: queued before the presplit runs, beside them
-    // (OSPF_KSP_DECR_AFTER=1: after their first traversal round -- measured
-    // slower, 22.9 vs 20.4 ms per F100k launch: the presplit chain is not
-    // the longer one once it shares the chip)
-    bool decr_queued = false;
-    auto launch_decr = [&]() -> int {
-      if (decr_queued) return OSPF_OK;
-      decr_queued = true;
-      if (ks != s) {  // (the first round's traversal done: ordered on fs)
-        HIPCHK(c, hipEventRecord(c->ksp_ev[0], fs));
-        HIPCHK(c, hipStreamWaitEvent(ks, c->ksp_ev[0], 0));
-      }
-      hipError_t e3 = ospf::launch_ksp_decr(c->g, td, nblk, ks);
-      if (e3 != hipSuccess) return hip_fail(c, e3, "launch_ksp_decr");
-      if (npre) {  // the decremental kernel's fallback count (ctr[13]), then its event
-        HIPCHK(c, hipMemcpyAsync(d_ctr + 13, d_ctr + 1, 4, hipMemcpyDeviceToDevice, ks));
-        HIPCHK(c, hipEventRecord(c->ksp_ev[3], ks));
-      }
-      if (td.budget) {
-        e3 = ospf::launch_ksp_decr_heavy(c->g, td, hblk, ks);
-        if (e3 != hipSuccess) return hip_fail(c, e3, "launch_ksp_decr_heavy");
-      }
-      return OSPF_OK;
-    };
-    const bool decr_first = !npre || getenv("OSPF_KSP_DECR_AFTER") == nullptr;
-    if (decr_first && (rc = launch_decr())) return rc;
+    // (after their first traversal round measured slower, 22.9 vs 20.4 ms per
+    // F100k launch: the presplit chain is not the longer one once it shares
+    // the chip)
+    if (ks != s) {  // (ordered behind fs)
+      HIPCHK(c, hipEventRecord(c->ksp_ev[0], fs));
+      HIPCHK(c, hipStreamWaitEvent(ks, c->ksp_ev[0], 0));
+    }
+    e = ospf::launch_ksp_decr(c->g, td, nblk, ks);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_ksp_decr");
+    if (npre) {  // the decremental kernel's fallback count (ctr[13]), then its event
+      HIPCHK(c, hipMemcpyAsync(d_ctr + 13, d_ctr + 1, 4, hipMemcpyDeviceToDevice, ks));
+      HIPCHK(c, hipEventRecord(c->ksp_ev[3], ks));
+    }
+    if (td.budget) {
+      e = ospf::launch_ksp_decr_heavy(c->g, td, hblk, ks);
+      if (e != hipSuccess) return hip_fail(c, e, "launch_ksp_decr_heavy");
+    }
     // a list of runs through full_reruns on s: compacted (dsts, status,
     // ignore sets, counts) into scratch slot `slot`, records scattered back
     // fold: before the last round, runs of a second list (the decremental
@@ -914,8 +871,7 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
     // scattered back with it
     const uint32_t* fold_list = nullptr;
     uint32_t folded = 0;
-    auto rerun_list = [&](const uint32_t* d_list, uint32_t nl, int slot,
-                          const std::function<int()>& after_first = nullptr, uint32_t extra = 0,
+    auto rerun_list = [&](const uint32_t* d_list, uint32_t nl, int slot, uint32_t extra = 0,
                           const std::function<int(const uint32_t**, uint32_t*)>& fold = nullptr) -> int {
       const uint32_t cap_n = nl + extra;
       const size_t sz_fd = align_up(cap_n * 4ull, 256), sz_fr = align_up((size_t)cap_n * cap * 4ull, 256);
@@ -958,7 +914,7 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
           Rn += n2;
           return OSPF_OK;
         };
-      rc2 = full_reruns(f_dsts, nl, f_ign, f_cnt, f_status, f_k2, after_first, before_last);
+      rc2 = full_reruns(f_dsts, nl, f_ign, f_cnt, f_status, f_k2, before_last);
       if (rc2) return rc2;
       if ((rc2 = scatter(0, d_list, nl))) return rc2;
       if (n2 && (rc2 = scatter(nl, l2, n2))) return rc2;
@@ -967,39 +923,21 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
       return OSPF_OK;
     };
     if (npre) {  // beside the decremental kernels
-      // OSPF_KSP_PRESORT=1: longest ignore lists (most k = 1 paths) first
-      // (measured 21.3 vs 21.1 ms as found: off)
-      const char* ps = getenv("OSPF_KSP_PRESORT");
-      if (ps && atoi(ps) != 0) {
-        std::vector<uint32_t> pre(npre), cnt(n);
-        HIPCHK(c, hipMemcpyAsync(pre.data(), d_pre, npre * 4ull, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(cnt.data(), d_cnt, n * 4ull, hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));
-        std::stable_sort(pre.begin(), pre.end(), [&](uint32_t a, uint32_t b) {
-          return cnt[a] != cnt[b] ? cnt[a] > cnt[b] : a < b;
-        });
-        HIPCHK(c, hipMemcpyAsync(d_pre, pre.data(), npre * 4ull, hipMemcpyHostToDevice, fs));
-        HIPCHK(c, hipStreamSynchronize(fs));
-      }
-      // the decremental kernel's fallbacks join the last presplit round when
-      // that kernel is done by then (OSPF_KSP_NOFOLD: a round of their own
-      // after it, as before)
-      const bool fold_on = !getenv("OSPF_KSP_NOFOLD");
+      // the presplit runs as found (longest ignore lists first measured 21.3
+      // vs 21.1 ms); the decremental kernel's fallbacks join their last round
+      // when that kernel is done by then
       auto fold = [&](const uint32_t** l, uint32_t* m) -> int {
         *l = d_fb;
         *m = 0;
-        if (!decr_queued || hipEventQuery(c->ksp_ev[3]) != hipSuccess) return OSPF_OK;
+        if (hipEventQuery(c->ksp_ev[3]) != hipSuccess) return OSPF_OK;
         uint32_t cnt = 0;
         HIPCHK(c, hipMemcpy(&cnt, d_ctr + 13, 4, hipMemcpyDeviceToHost));
         *m = cnt;
         return OSPF_OK;
       };
       constexpr uint32_t kFold = 256;  // fallbacks a presplit round takes
-      rc = fold_on ? rerun_list(d_pre, npre, 3, launch_decr, kFold, fold)
-                   : rerun_list(d_pre, npre, 3, launch_decr);
-      if (rc) return rc;
+      if ((rc = rerun_list(d_pre, npre, 3, kFold, fold))) return rc;
     }
-    if ((rc = launch_decr())) return rc;  // (no round called it)
     uint32_t ctr[32] = {};
     HIPCHK(c, hipMemcpyAsync(ctr, d_ctr, 128, hipMemcpyDeviceToHost, ks));
     HIPCHK(c, hipStreamSynchronize(ks));
@@ -1025,7 +963,7 @@ int run_ksp2(ospf_ctx* c, const ospf_ksp2* k, hipStream_t s) {
                 k->dsts ? 0u : 0u, (l[1] - t0) / 1e5, (l[2] - l[1]) / 1e5, (l[3] - l[2]) / 1e5);
       }
     }
-    if (getenv("OSPF_KSP_DEBUG")) {
+    if (knob_set(Knob::OSPF_KSP_DEBUG)) {
       uint64_t clk[8];
       memcpy(clk, ctr + 16, sizeof(clk));
       // wave-ms: wall-clock ms (100 MHz) summed over the waves / blocks
@@ -1178,7 +1116,7 @@ static void cover_closure_split(ospf_ctx* c) {
   c->cl_comp_of.assign(nS, ~0u);
   c->cl_comp_off.assign(1, 0u);
   c->cl_comp_mem.clear();
-  if (getenv("OSPF_COVER_NOCLOSURE") || nS < 2) return;
+  if (knob_flag(Knob::OSPF_COVER_NOCLOSURE) || nS < 2) return;
   const auto& crow = c->h_ccrow;
   const auto& ced = c->h_cedge;
   std::vector<uint32_t> deg(nS), dd;
@@ -1216,7 +1154,7 @@ static void cover_closure_split(ospf_ctx* c) {
     bool fits = true;
     for (uint32_t i = 0; i < nS && fits; ++i)
       if (deg[i] < tau && sz[find(i)] > ospf::kClosureMaxK) fits = false;
-    if (getenv("OSPF_SWEEP_DEBUG"))
+    if (knob_flag(Knob::OSPF_SWEEP_DEBUG))
       fprintf(stderr, "cover split: nS %u tau %u seeds %u fits %d\n", nS, tau, ns, (int)fits);
     if (!fits) continue;
     std::vector<uint32_t> id(nS, ~0u), cnt;
@@ -1541,7 +1479,7 @@ int ospf_load_graph(ospf_ctx* c, const ospf_csr* csr, uint64_t version) {
   if (!c || !csr) return OSPF_E_INVAL;
   if (injected(c)) return OSPF_E_DEVICE;
   // OSPF_SWEEP_TIMING: host phases of the load on stderr
-  const bool tm = getenv("OSPF_SWEEP_TIMING") != nullptr;
+  const bool tm = knob_flag(Knob::OSPF_SWEEP_TIMING);
   auto tl = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!tm) return;
@@ -1906,7 +1844,7 @@ int ospf_plan_n(const ospf_ctx* c, uint32_t flags, uint32_t nh_words, uint32_t m
   out->lds_bytes = (uint32_t)p.lds;
   if (p.variant == 5) {
     const uint32_t kcap = max_root_neighbors ? std::min(max_root_neighbors, 32u * W) : 32u * W;
-    out->slices = ms_shape(n_roots, kcap, c->depth_bound <= 253 && getenv("OSPF_MS_PACK")).npass;
+    out->slices = ms_shape(n_roots, kcap, c->depth_bound <= 253 && knob_flag(Knob::OSPF_MS_PACK)).npass;
   } else {
     out->slices = (p.variant == 3 || p.variant == 4) ? ospf::bfs_slices(W) : 1u;
   }
@@ -2086,135 +2024,75 @@ int levels_dev(ospf_ctx* c, const uint32_t* d_roots, uint32_t n, uint32_t flags,
     return fail(c, OSPF_E_RANGE, "level rows need a depth bound <= 123");
   hipStream_t s = (hipStream_t)stream;
   const uint32_t V = c->info.n_nodes, lmax = c->depth_bound + 2;
-  if (!getenv("OSPF_LV64")) {  // 128-root traversals (spf_levels.hip)
-    // per wide batch: frontier slots 2 x 16 B, seen 16 B, accb 16 B, records 128 B;
-    // two state buffers: the rows kernel of round k (on lv_aux) runs beside
-    // the traversal of round k + 1 (on the caller's stream): the traversal is
-    // latency-bound, the rows kernel store-bound
-    const size_t per_wb = align_up((size_t)V * 16ull * 4 + V * 128ull + lmax * 8ull, 256);
-    uint32_t nb_cap = 192;
-    if (const char* e = getenv("OSPF_LV_NB")) nb_cap = std::max(1, atoi(e));
-    const bool overlap = !getenv("OSPF_LV_SERIAL");
-    const size_t nbuf = overlap ? 2 : 1;
-    nb_cap = (uint32_t)std::max<size_t>(1, std::min<size_t>(nb_cap, (6ull << 30) / (per_wb * nbuf)));
-    const uint32_t total = (n + 127) / 128, nb_max = std::min(nb_cap, total);
-    int rc = OSPF_OK;
-    char* sp = stream_scratch(c, s, per_wb * nb_max * nbuf, &rc);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (overlap && !c->lv_aux) {
-      HIPCHK(c, hipStreamCreateWithFlags(&c->lv_aux, hipStreamNonBlocking));
-      for (hipEvent_t& e : c->lv_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    ospf::LvArgs a{};
-    a.roots = d_roots;
-    a.n = n;
-    a.lmax = lmax;
-    a.dbound = depth_cap ? std::min(depth_cap, c->depth_bound) : c->depth_bound;
-    a.maxd = d_maxd;
-    a.push_div = 16;
-    if (const char* e = getenv("OSPF_MS_PUSH_DIV")) a.push_div = (uint32_t)std::max(0, atoi(e));
-    a.masked = 0;
-    if (const char* e = getenv("OSPF_LV_MASKED")) a.masked = (uint32_t)atoi(e);
-    a.dist = d_dist;
-    a.dpitch = dist_pitch;
-    a.levrow = d_lev;
-    a.lev_pitch = lev_pitch;
-    a.digest = d_lev_digest;
-    a.err = c->d_err;
-    if (d_lev_digest) HIPCHK(c, ospf::zero_async(d_lev_digest, (size_t)n * sizeof(ospf_digest), s));
-    uint32_t k = 0;
-    for (uint32_t vb0 = 0; vb0 < total; vb0 += nb_max, ++k) {
-      const uint32_t buf = overlap ? (k & 1u) : 0u;
-      char* base = sp + per_wb * nb_max * buf;
-      a.vb0 = vb0;
-      a.nb = std::min(nb_max, total - vb0);
-      a.front = (uint4*)base;
-      a.seen = a.front + 2ull * a.nb * V;
-      a.accb = a.seen + (size_t)a.nb * V;
-      a.lev = (uint8_t*)(a.accb + (size_t)a.nb * V);
-      a.found = (uint32_t*)(a.lev + (size_t)a.nb * V * 128ull);
-      a.mass = a.found + (size_t)a.nb * lmax;
-      // the buffer's previous rows kernel (round k - 2) must be done with it
-      if (overlap && k >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->lv_ev[2 + buf], 0));
-      // zero frontier slot 1, seen, accb (contiguous) and found / mass; slot 0
-      // is written whole by every level before it is read; records are not
-      // cleared (set once per (node, root), read masked by seen)
-      HIPCHK(c, ospf::zero_async(a.front + (size_t)a.nb * V, (size_t)a.nb * V * 16ull * 3, s));
-      HIPCHK(c, ospf::zero_async(a.found, (size_t)a.nb * lmax * 8ull, s));
-      hipError_t e = ospf::launch_levels128_traverse(c->g, a, s);
-      if (e != hipSuccess) return hip_fail(c, e, "launch_levels128_traverse");
-      if (overlap) {
-        HIPCHK(c, hipEventRecord(c->lv_ev[buf], s));
-        HIPCHK(c, hipStreamWaitEvent(c->lv_aux, c->lv_ev[buf], 0));
-        e = ospf::launch_levels128_rows(c->g, a, c->lv_aux);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_levels128_rows");
-        HIPCHK(c, hipEventRecord(c->lv_ev[2 + buf], c->lv_aux));
-      } else {
-        e = ospf::launch_levels128_rows(c->g, a, s);
-        if (e != hipSuccess) return hip_fail(c, e, "launch_levels128_rows");
-      }
-    }
-    if (overlap) {  // the caller's stream sees every rows kernel done
-      HIPCHK(c, hipEventRecord(c->lv_ev[2], c->lv_aux));
-      HIPCHK(c, hipStreamWaitEvent(s, c->lv_ev[2], 0));
-    }
-    c->spf_runs += n;
-    return OSPF_OK;
-  }
-  // per batch: frontier slots 2 x 8 B, seen 8 B, accb 8 B, level records 64 B
-  const size_t per_vb = align_up((size_t)V * 8ull * 4 + V * 64ull + lmax * 8ull, 256);
-  uint32_t nb_cap = 96;
-  if (const char* e = getenv("OSPF_MS_NB")) nb_cap = std::max(1, atoi(e));
-  nb_cap = (uint32_t)std::max<size_t>(1, std::min<size_t>(nb_cap, (6ull << 30) / per_vb));
-  const uint32_t total_vb = (n + 63) / 64;
-  const uint32_t nb_max = std::min(nb_cap, total_vb);
+  // 128-root traversals (spf_levels.hip)
+  // per wide batch: frontier slots 2 x 16 B, seen 16 B, accb 16 B, records 128 B;
+  // two state buffers: the rows kernel of round k (on lv_aux) runs beside
+  // the traversal of round k + 1 (on the caller's stream): the traversal is
+  // latency-bound, the rows kernel store-bound
+  const size_t per_wb = align_up((size_t)V * 16ull * 4 + V * 128ull + lmax * 8ull, 256);
+  uint32_t nb_cap = (uint32_t)knob_int(Knob::OSPF_LV_NB);
+  const bool overlap = !knob_flag(Knob::OSPF_LV_SERIAL);
+  const size_t nbuf = overlap ? 2 : 1;
+  nb_cap = (uint32_t)std::max<size_t>(1, std::min<size_t>(nb_cap, (6ull << 30) / (per_wb * nbuf)));
+  const uint32_t total = (n + 127) / 128, nb_max = std::min(nb_cap, total);
   int rc = OSPF_OK;
-  char* sp = stream_scratch(c, s, per_vb * nb_max, &rc);
+  char* sp = stream_scratch(c, s, per_wb * nb_max * nbuf, &rc);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  uint32_t push_div = 8;
-  if (const char* e = getenv("OSPF_MS_PUSH_DIV")) push_div = (uint32_t)std::max(0, atoi(e));
-  if (dist_pitch && dist_pitch != V)
-    return fail(c, OSPF_E_INVAL, "levels (OSPF_LV64): dist rows of pitch V only");
-  ospf::MsArgs a{};
+  if (overlap && !c->lv_aux) {
+    HIPCHK(c, hipStreamCreateWithFlags(&c->lv_aux, hipStreamNonBlocking));
+    for (hipEvent_t& e : c->lv_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  ospf::LvArgs a{};
   a.roots = d_roots;
   a.n = n;
-  a.W = 1u << 26;  // no next-hop words: every root width passes the init check
-  a.npass = 1;
-  a.R = 64;
-  a.PP = a.OW = 1;
-  a.rep = 1;
   a.lmax = lmax;
-  a.dbound = c->depth_bound;
-  a.kcap = 0xFFFFFFFFu;
-  a.push_div = push_div;
-  a.defer = 1;
-  a.merged = 0;
-  a.err = c->d_err;
+  a.dbound = depth_cap ? std::min(depth_cap, c->depth_bound) : c->depth_bound;
+  a.maxd = d_maxd;
+  a.push_div = (uint32_t)knob_int(Knob::OSPF_MS_PUSH_DIV, 16);
+  a.masked = (uint32_t)knob_int(Knob::OSPF_LV_MASKED);
   a.dist = d_dist;
+  a.dpitch = dist_pitch;
   a.levrow = d_lev;
   a.lev_pitch = lev_pitch;
   a.digest = d_lev_digest;
+  a.err = c->d_err;
   if (d_lev_digest) HIPCHK(c, ospf::zero_async(d_lev_digest, (size_t)n * sizeof(ospf_digest), s));
-  for (uint32_t vb0 = 0; vb0 < total_vb; vb0 += nb_max) {
+  uint32_t k = 0;
+  for (uint32_t vb0 = 0; vb0 < total; vb0 += nb_max, ++k) {
+    const uint32_t buf = overlap ? (k & 1u) : 0u;
+    char* base = sp + per_wb * nb_max * buf;
     a.vb0 = vb0;
-    a.nb = std::min(nb_max, total_vb - vb0);
-    a.front = (uint64_t*)sp;  // distances only: 8-B records, slots d & 1
+    a.nb = std::min(nb_max, total - vb0);
+    a.front = (uint4*)base;
     a.seen = a.front + 2ull * a.nb * V;
     a.accb = a.seen + (size_t)a.nb * V;
-    a.planes = nullptr;
     a.lev = (uint8_t*)(a.accb + (size_t)a.nb * V);
-    a.found = (uint32_t*)(a.lev + (size_t)a.nb * V * 64ull);
+    a.found = (uint32_t*)(a.lev + (size_t)a.nb * V * 128ull);
     a.mass = a.found + (size_t)a.nb * lmax;
-    // zero: frontier slot 1 (the init kernel ORs level 1 into it; slot 0 is
-    // written whole by every level before it is read), seen, accb, found /
-    // mass. The level records are not cleared: their bytes are set once per
-    // (node, root) and read masked by seen.
-    HIPCHK(c, ospf::zero_async(a.front + (size_t)a.nb * V, (size_t)a.nb * V * 8ull * 3, s));
+    // the buffer's previous rows kernel (round k - 2) must be done with it
+    if (overlap && k >= 2) HIPCHK(c, hipStreamWaitEvent(s, c->lv_ev[2 + buf], 0));
+    // zero frontier slot 1, seen, accb (contiguous) and found / mass; slot 0
+    // is written whole by every level before it is read; records are not
+    // cleared (set once per (node, root), read masked by seen)
+    HIPCHK(c, ospf::zero_async(a.front + (size_t)a.nb * V, (size_t)a.nb * V * 16ull * 3, s));
     HIPCHK(c, ospf::zero_async(a.found, (size_t)a.nb * lmax * 8ull, s));
-    hipError_t e = ospf::launch_msbfs_levels(c->g, a, c->depth_bound, s);
-    if (e != hipSuccess) return hip_fail(c, e, "launch_msbfs_levels");
+    hipError_t e = ospf::launch_levels128_traverse(c->g, a, s);
+    if (e != hipSuccess) return hip_fail(c, e, "launch_levels128_traverse");
+    if (overlap) {
+      HIPCHK(c, hipEventRecord(c->lv_ev[buf], s));
+      HIPCHK(c, hipStreamWaitEvent(c->lv_aux, c->lv_ev[buf], 0));
+      e = ospf::launch_levels128_rows(c->g, a, c->lv_aux);
+      if (e != hipSuccess) return hip_fail(c, e, "launch_levels128_rows");
+      HIPCHK(c, hipEventRecord(c->lv_ev[2 + buf], c->lv_aux));
+    } else {
+      e = ospf::launch_levels128_rows(c->g, a, s);
+      if (e != hipSuccess) return hip_fail(c, e, "launch_levels128_rows");
+    }
+  }
+  if (overlap) {  // the caller's stream sees every rows kernel done
+    HIPCHK(c, hipEventRecord(c->lv_ev[2], c->lv_aux));
+    HIPCHK(c, hipStreamWaitEvent(s, c->lv_ev[2], 0));
   }
   c->spf_runs += n;
   return OSPF_OK;
@@ -2250,7 +2128,7 @@ int ospf_nh_derive_dev(ospf_ctx* c, const uint32_t* d_roots, uint32_t n, uint32_
   d.pitch = lev_pitch;
   d.pos = d_lev_pos;
   d.lev_digest = d_lev_digest;
-  if (const char* e = getenv("OSPF_DERIVE_CTILES")) d.ctiles = (uint32_t)std::max(1, atoi(e));
+  d.ctiles = (uint32_t)knob_int(Knob::OSPF_DERIVE_CTILES, (int)d.ctiles);
   d.nh = d_nh;
   d.digest = d_digest;
   d.err = c->d_err;
@@ -2317,7 +2195,7 @@ int nh_derive_twin_launch(ospf_ctx* c, const uint32_t* d_roots, uint32_t n, uint
   // (a pitch that is not a multiple of 4 words takes the kernels' 4-B stores)
   if (nh_pitch && nh_pitch < c->info.n_nodes * nh_words)
     return fail(c, OSPF_E_INVAL, "twin derive: next-hop row pitch < V * nh_words");
-  if (const char* e = getenv("OSPF_TWIN_CTILES")) a.ctiles = (uint32_t)std::max(1, atoi(e));
+  a.ctiles = (uint32_t)knob_int(Knob::OSPF_TWIN_CTILES, (int)a.ctiles);
   hipError_t e = ospf::launch_nh_derive_twin(c->g, a, s);
   if (e != hipSuccess) return hip_fail(c, e, "launch_nh_derive_twin");
   return OSPF_OK;
@@ -2452,9 +2330,9 @@ int leaf_derive(ospf_ctx* c, const uint32_t* d_roots, uint32_t n, const uint32_t
   a.nh = d_nh;
   a.digest = d_digest;
   a.err = c->d_err;
-  if (const char* e = getenv("OSPF_LEAF_CTILES")) a.ctiles = (uint32_t)std::max(1, atoi(e));
+  a.ctiles = (uint32_t)knob_int(Knob::OSPF_LEAF_CTILES, (int)a.ctiles);
   if (group_major >= 0) a.group_major = group_major ? 1u : 0u;  // the sweep's choice
-  if (const char* e = getenv("OSPF_LEAF_GROUP_MAJOR")) a.group_major = atoi(e) ? 1u : 0u;
+  if (knob_set(Knob::OSPF_LEAF_GROUP_MAJOR)) a.group_major = knob_flag(Knob::OSPF_LEAF_GROUP_MAJOR) ? 1u : 0u;
   a.dpitch = dist_pitch;
   a.npitch = nh_pitch;
   hipError_t e = ospf::launch_leaf_derive(c->g, a, max_root_neighbors ? max_root_neighbors : 32u, s);
@@ -2543,14 +2421,14 @@ int ospf_wderive_dev(ospf_ctx* c, const uint32_t* d_roots, uint32_t n, uint32_t 
   a.err = c->d_err;
   const uintptr_t al = (uintptr_t)d_src | (uintptr_t)d_dist | (uintptr_t)d_nh;
   a.vec = (V % 4u == 0 && src_pitch % 4u == 0 && (al & 15u) == 0) ? 1u : 0u;
-  if (const char* e = getenv("OSPF_WD_G")) a.G = (uint32_t)std::max(1, atoi(e));
-  if (const char* e = getenv("OSPF_WD_CTILES")) a.ctiles = (uint32_t)std::max(1, atoi(e));
+  a.G = (uint32_t)knob_int(Knob::OSPF_WD_G, (int)a.G);
+  a.ctiles = (uint32_t)knob_int(Knob::OSPF_WD_CTILES, (int)a.ctiles);
   // slot table width from the caller's bound (the roots' distinct neighbour
   // counts are checked on the device: a wider root raises error bit 1)
   if (max_root_neighbors > ospf::kWdMaxK)
     return fail(c, OSPF_E_RANGE, "wderive: leaf roots have at most 32 distinct neighbours");
   uint32_t kmax = max_root_neighbors ? max_root_neighbors : ospf::kWdMaxK;
-  if (const char* e = getenv("OSPF_WD_KMAX")) kmax = (uint32_t)std::max(1, atoi(e));
+  kmax = (uint32_t)knob_int(Knob::OSPF_WD_KMAX, (int)kmax);
   hipError_t e = ospf::launch_wderive(c->g, a, kmax, s);
   if (e != hipSuccess) return hip_fail(c, e, "launch_wderive");
   c->spf_runs += n;
@@ -2600,10 +2478,9 @@ int ospf_int::wderive_wide(ospf_ctx* c, const uint32_t* d_roots, uint32_t n, uin
   const uintptr_t al = (uintptr_t)d_src | (uintptr_t)d_nh;
   a.vec = (V % 4u == 0 && src_pitch % 4u == 0 && (al & 15u) == 0) ? 1u : 0u;
   a.ctiles = ctiles;
-  if (const char* e = getenv("OSPF_WD_CTILES")) a.ctiles = (uint32_t)std::max(1, atoi(e));
-  if (const char* e = getenv(nh_words > 4 ? "OSPF_WL_CTILES" : "OSPF_WW_CTILES"))
-    a.ctiles = (uint32_t)std::max(1, atoi(e));
-  if (const char* e = getenv("OSPF_WD_G")) a.G = (uint32_t)std::max(1, atoi(e));
+  a.ctiles = (uint32_t)knob_int(Knob::OSPF_WD_CTILES, (int)a.ctiles);
+  a.ctiles = (uint32_t)knob_int(nh_words > 4 ? Knob::OSPF_WL_CTILES : Knob::OSPF_WW_CTILES, (int)a.ctiles);
+  a.G = (uint32_t)knob_int(Knob::OSPF_WD_G, (int)a.G);
   hipError_t e = ospf::launch_wderive_wide(c->g, a, nh_words, s);
   if (e != hipSuccess) return hip_fail(c, e, "launch_wderive_wide");
   return OSPF_OK;

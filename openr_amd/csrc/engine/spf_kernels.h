@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../../include/openr_spf.h"
+#include "../common/knobs.h"
 
 namespace ospf {
 
@@ -235,8 +236,6 @@ struct MsArgs {
   // whose every run has reached its destination stops after that level (the
   // k = 2 trace reads only levels below the destination's)
   const uint32_t* kdst;
-  uint8_t* levrow;        // derive phase 1 (kp -1): [n][lev_pitch] dist + 1 per (run, node)
-  uint32_t lev_pitch;     //   bytes per level row (multiple of 16, >= V; padding zeroed)
 };
 
 // Derive phase 2 (nh_derive_kernel): next-hop words of n roots from the level
@@ -271,8 +270,6 @@ struct WidePlan {
   uint32_t* nh;           // [n][V][W]
   ospf_digest* digest;    // [n] (zeroed by the launcher) or null
   uint32_t tiles, ctiles, chunks;  // set by the launcher (ctiles 0: its choice)
-  uint32_t late_keys;     // set by the launcher: OSPF_WIDE_LATE_KEYS (A/B)
-  uint32_t st16;          // set by the launcher: records staged, 16-B stores (A/B)
 };
 hipError_t launch_wide_plan(const DevGraph& g, const WidePlan& p, hipStream_t s);
 
@@ -498,9 +495,6 @@ hipError_t launch_wnh_hub(const DevGraph& g, const HubPlan& p, hipStream_t s);
 // cover roots (<= 128 distinct neighbours): next-hop words [n][V][W] (W <= 4)
 // + digests from the neighbours' rows and the root's own row (all in src)
 hipError_t launch_wderive_wide(const DevGraph& g, WDeriveArgs a, uint32_t W, hipStream_t s);
-// phase 1: distances only (kp -1) + msbfs_levrows; phase 2: nh_derive
-hipError_t launch_msbfs_levels(const DevGraph& g, const MsArgs& a, uint32_t depth_bound,
-                               hipStream_t s);
 hipError_t launch_nh_derive(const DevGraph& g, const DeriveArgs& d, hipStream_t s);
 
 // Twin derive (spf_twin.hip): next-hop words (W <= 4) of roots whose
@@ -529,7 +523,6 @@ struct TwinArgs {
   uint32_t* dist;
   uint32_t dpitch;        // 0: V
   uint32_t npitch;        // next-hop row pitch in words (0: V * W)
-  uint32_t bsearch;       // set by the launcher: OSPF_TWIN4_BSEARCH (A/B)
   // twin_levels_kernel: the roots' own rows at pos[root]
 };
 hipError_t launch_nh_derive_twin(const DevGraph& g, const TwinArgs& a, hipStream_t s);
@@ -654,12 +647,10 @@ struct TraceArgs {
   uint32_t budget;          // DFS steps before a run goes to the heavy kernel (0 = none)
   uint32_t look;            // lookahead: predecessors with rows <= look entries are probed
   uint32_t src_cut;         // presplit: runs ignoring more of the source's links (0: off)
-  uint32_t decr_runs;       // ksp_decr: runs per block (0: persistent blocks)
   uint32_t* pre_bits;       // [n / 32] runs the presplit sent to the full reruns (ksp_decr skips them)
   uint32_t* heavy;          // [n] queued run indices
   uint32_t* heavy_ctr;      // [2] {queued, taken}, zeroed by the caller
   unsigned long long* hlog; // debug (OSPF_KSP_DEBUG=2): [n][4] {run, start, traced, end} clocks of heavy runs
-  uint32_t map_fb;          // runs past the decremental map budget: 1 = the full reruns, 0 = the heavy kernel
   // decremental reruns (launch_ksp_decr): rows = the source's dist row
   const uint32_t* tc;       // [V] hint: link of each node's last support (launch_ksp_hint)
   uint32_t* fb;             // [n] runs left to the full masked reruns
@@ -718,7 +709,7 @@ hipError_t launch_fill32(uint32_t* a, size_t n, uint32_t v, hipStream_t s);
 // OSPF_ZERO_MEMSET=1 restores hipMemsetAsync (the round-4 behaviour), for
 // the A/B of scripts/debug/memset_nodes.py.
 inline bool zero_by_memset() {
-  static const bool m = getenv("OSPF_ZERO_MEMSET") != nullptr;
+  static const bool m = knob_flag(Knob::OSPF_ZERO_MEMSET);
   return m;
 }
 inline hipError_t zero_async(void* p, size_t bytes, hipStream_t s) {

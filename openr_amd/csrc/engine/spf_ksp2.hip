@@ -973,9 +973,7 @@ __global__ void __launch_bounds__(64) ksp_decr_kernel(DevGraph g, TraceArgs t) {
   const uint32_t lane = threadIdx.x;
   const uint32_t src = t.src;
   uint32_t* dead = t.dead + (size_t)blockIdx.x * t.dead_words;
-  // persistent (decr_runs 0: until the runs are taken), or decr_runs runs per
-  // block so a higher-priority stream's blocks get the CUs as blocks retire
-  for (uint32_t it = 0; t.decr_runs == 0 || it < t.decr_runs; ++it) {
+  for (;;) {  // persistent: until the runs are taken
     if (lane == 0) L.run = atomicAdd(&t.ctr[0], 1u);
     __builtin_amdgcn_wave_barrier();
     const uint32_t i = ((volatile uint32_t&)L.run);
@@ -1006,21 +1004,12 @@ __global__ void __launch_bounds__(64) ksp_decr_kernel(DevGraph g, TraceArgs t) {
       if (prep) atomicAdd((unsigned long long*)&clk[1], (unsigned long long)(c1 - t3));
     }
     if (!prep) {
-      // past the map or pending-node budget: the 16-wave kernel redoes it
-      // with 8x budgets and traces it from the start; past the affected-set,
-      // edge or ignore-list budget (a large change, whose single-wave
-      // prepare there would be slow: OSPF_KSP_SRCCUT=0 at F100k sends 7 such
-      // runs and takes 58 ms): the full reruns
-      if (t.budget && !t.map_fb && ((volatile uint32_t&)L.why) == 0u &&
-          ((volatile uint32_t&)L.naff) <= DecrSmall::kAff) {
-        if (lane == 0) {
-          out[0] = 0u;
-          atomicAdd(&t.ctr[2], 1u);  // (decided there; un-counted if it falls back)
-          t.heavy[atomicAdd(&t.heavy_ctr[0], 1u)] = i;
-        }
-      } else {
-        fallback();
-      }
+      // past a budget (map, pending nodes, affected set, edges or ignore
+      // list): the full reruns; with presplit runs it joins their last round.
+      // (The 16-wave kernel redoing map-budget runs with 8x budgets had one
+      // slow run, 10.8 ms at F100k, end the launch: 20.17 -> 20.04 ms,
+      // profiles/r06/h1_ksp2_order_ab.txt.)
+      fallback();
       continue;
     }
     const uint32_t dst = t.dsts[i];

@@ -317,20 +317,12 @@ hipError_t launch_leaf_derive(const DevGraph& g, const LeafArgs& a0, uint32_t km
   const uint32_t chunks = (a.tiles + a.ctiles - 1) / a.ctiles;
   a.chunks = chunks;
   const dim3 grid(a.ngroups * chunks);
-  // two tiles of neighbour loads in flight (OSPF_LEAF_PD=1: one; read per
-  // launch for in-process A/B: 19.61 vs 19.71 ms per F100k sweep,
-  // profiles/r06/i1_leaf_prefetch_ab.txt)
-  const char* pe = getenv("OSPF_LEAF_PD");
-  const bool pd2 = !pe || atoi(pe) >= 2;
-  // the tile's digest keys one tile ahead with the neighbour words
-  // (OSPF_LEAF_KD=0: loaded at the digest terms; 20.26 -> 19.48 ms per F100k
-  // sweep in one process, profiles/r06/k3_leaf_key_prefetch_ab.txt)
-  const char* ke = getenv("OSPF_LEAF_KD");
-  const bool kd = !ke || atoi(ke) != 0;
+  // kmax <= 8: two tiles of neighbour loads in flight (19.61 vs 19.71 ms per
+  // F100k sweep with one, profiles/r06/i1_leaf_prefetch_ab.txt) and the tile's
+  // digest keys one tile ahead with the neighbour words (20.26 -> 19.48 ms,
+  // profiles/r06/k3_leaf_key_prefetch_ab.txt)
   if (kmax <= 8) {
-    if (pd2 && kd) hipLaunchKernelGGL((leaf_derive_kernel<8, 2, true>), grid, dim3(kBlock), 0, s, g, a);
-    else if (pd2) hipLaunchKernelGGL((leaf_derive_kernel<8, 2>), grid, dim3(kBlock), 0, s, g, a);
-    else hipLaunchKernelGGL((leaf_derive_kernel<8, 1>), grid, dim3(kBlock), 0, s, g, a);
+    hipLaunchKernelGGL((leaf_derive_kernel<8, 2, true>), grid, dim3(kBlock), 0, s, g, a);
   } else if (kmax <= 16) {
     hipLaunchKernelGGL((leaf_derive_kernel<16, 1>), grid, dim3(kBlock), 0, s, g, a);
   } else {

@@ -850,8 +850,8 @@ __global__ void __launch_bounds__(256) msbfs_rows_multi_kernel(DevGraph g, MsArg
 
 // ---------------------------------------------------------------- derive
 // All-sources next hops from neighbour levels (unit metric / hop count).
-// Phase 1 (distances only, KP = -1): msbfs_levrows writes each batch's levels
-// as byte rows lev[run][node] = dist + 1 (0 = unreached) and the dist rows.
+// Phase 1 (spf_levels.hip): each batch's levels as byte rows lev[run][node] =
+// dist + 1 (0x7F = unreached) and the dist rows.
 // Phase 2 (nh_derive): the next hops of root r towards v are the distinct
 // neighbours n_k of r with an up link r-n_k, n_k transit or n_k == v, and
 // dist(n_k, v) = dist(r, v) - 1 -- exactly the reference's nextHops
@@ -859,155 +859,6 @@ __global__ void __launch_bounds__(256) msbfs_rows_multi_kernel(DevGraph g, MsArg
 // tail from n is a shortest n -> v path with transit intermediates, and
 // whose length is 1 + dist(n, v)). No bit-planes, one traversal per 64 roots
 // whatever their width, and the next-hop words are written once, whole.
-__device__ __forceinline__ uint32_t byte_perm(uint32_t hi, uint32_t lo, uint32_t sel) {
-  return __builtin_amdgcn_perm(hi, lo, sel);
-}
-// 0x01 in byte i for bit i of a nibble
-__device__ __forceinline__ uint32_t nib_bytes(uint32_t nib) {
-  return (nib * 0x00204081u) & 0x01010101u;
-}
-// one step of a transposing wave reduction: N values per lane, lanes paired
-// across offset o; afterwards value i (< N/2) of a lane is the pair's sum of
-// value i + (lane & o ? N/2 : 0)
-template <int N, typename T>
-__device__ __forceinline__ void xreduce_step(T* v, uint32_t lane, int o) {
-  const bool up = lane & (uint32_t)o;
-#pragma unroll
-  for (int i = 0; i < N / 2; ++i) {
-    const T send = up ? v[i] : v[i + N / 2];
-    const T keep = up ? v[i + N / 2] : v[i];
-    T recv;
-    if constexpr (sizeof(T) == 8) recv = shfl_xor64(send, o);
-    else recv = (T)__shfl_xor((int)send, o);
-    v[i] = keep + recv;
-  }
-}
-
-__global__ void __launch_bounds__(256) msbfs_levrows_kernel(DevGraph g, MsArgs a) {
-  // Block = (virtual batch, 512 nodes in two 256-node halves). Load: thread
-  // (quad q = tid % 64, root group rg = tid / 64: roots 16 rg .. 16 rg + 15)
-  // reads the 16-root slices of its four nodes' [node][root] records (bytes
-  // of roots not in seen[v] are stale: masked), transposes the 4 x 4 byte
-  // blocks with byte permutes and parks [root][quad] words (four nodes of one
-  // root) in LDS (row pitch 65 words: conflict-free both ways). Store: wave w
-  // takes roots 16 w .. 16 w + 15, lane = quad, so each store instruction
-  // writes 1 KB of consecutive dist row and 256 B of level row.
-  __shared__ uint32_t s_T[64 * 65];
-  const uint32_t vbl = blockIdx.x % a.nb;
-  const VB b(a, vbl, g.V, -1);
-  const uint32_t V = g.V, tid = threadIdx.x, q = tid & 63u, rg = tid >> 6;
-  const uint32_t vb0 = (blockIdx.x / a.nb) * 512u;
-  if (vb0 == 0 && tid == 0 && a.found[vbl * a.lmax + a.dbound + 1]) atomicOr(a.err, 8u);
-  const uint32_t nr = min(a.R, a.n - b.rix0);
-  uint32_t pk[16];        // per root of this wave: reached | sum dist << 16
-  uint64_t hh[16];        // per root: sum dist_key * (dist + 1)
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    pk[j] = 0u;
-    hh[j] = 0ull;
-  }
-  for (uint32_t half = 0; half < 2u; ++half) {
-    const uint32_t v0 = vb0 + 256u * half;
-    if (v0 >= V) break;  // block-uniform
-    const uint32_t vq = v0 + 4u * q;
-    {
-      uint32_t x[4][4];  // [node c][word m]: roots 16 rg + 4 m .. + 3 of node vq + c
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const uint32_t v = vq + c;
-        uint4 r4 = make_uint4(0u, 0u, 0u, 0u);
-        uint32_t sn = 0;
-        if (v < V) {
-          r4 = *reinterpret_cast<const uint4*>(a.lev + ((size_t)vbl * V + v) * 64u + 16u * rg);
-          sn = (uint32_t)(b.seen[v] >> (16u * rg)) & 0xFFFFu;
-        }
-        x[c][0] = r4.x & (nib_bytes(sn & 0xFu) * 0xFFu);
-        x[c][1] = r4.y & (nib_bytes((sn >> 4) & 0xFu) * 0xFFu);
-        x[c][2] = r4.z & (nib_bytes((sn >> 8) & 0xFu) * 0xFFu);
-        x[c][3] = r4.w & (nib_bytes((sn >> 12) & 0xFu) * 0xFFu);
-      }
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const uint32_t t0 = byte_perm(x[1][m], x[0][m], 0x05010400u);
-        const uint32_t t1 = byte_perm(x[1][m], x[0][m], 0x07030602u);
-        const uint32_t t2 = byte_perm(x[3][m], x[2][m], 0x05010400u);
-        const uint32_t t3 = byte_perm(x[3][m], x[2][m], 0x07030602u);
-        const uint32_t r0 = 16u * rg + 4u * m;
-        s_T[(r0 + 0u) * 65u + q] = byte_perm(t2, t0, 0x05040100u);
-        s_T[(r0 + 1u) * 65u + q] = byte_perm(t2, t0, 0x07060302u);
-        s_T[(r0 + 2u) * 65u + q] = byte_perm(t3, t1, 0x05040100u);
-        s_T[(r0 + 3u) * 65u + q] = byte_perm(t3, t1, 0x07060302u);
-      }
-    }
-    uint64_t kd[4] = {0ull, 0ull, 0ull, 0ull};
-    if (a.digest) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) kd[c] = vq + c < V ? g.dkey[2ull * (vq + c)] : 0ull;
-    }
-    __syncthreads();
-    const bool vec = (V & 3u) == 0 && vq + 4u <= V;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const uint32_t r = 16u * rg + j;  // rg = this wave
-      const uint32_t u = s_T[r * 65u + q];
-      if (r >= nr) continue;
-      // level row: dist + 1, 0x7F for unreached and padding (bytes < 0x80)
-      const uint32_t zm = ~((u | 0x80808080u) - 0x01010101u) & 0x80808080u;
-      if (vq < a.lev_pitch)
-        __builtin_nontemporal_store(
-            u | (zm - (zm >> 7)),
-            reinterpret_cast<uint32_t*>(a.levrow + (size_t)(b.rix0 + r) * a.lev_pitch + vq));
-      uint32_t dv[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const uint32_t l = (u >> (8 * c)) & 0xFFu;
-        dv[c] = l ? l - 1u : kInf;
-        if (a.digest && l) {
-          pk[j] += 1u + ((l - 1u) << 16);
-          hh[j] += kd[c] * (uint64_t)l;
-        }
-      }
-      if (a.dist) {
-        uint32_t* row = a.dist + (size_t)(b.rix0 + r) * V + vq;
-        if (vec) {
-          store_row16(row, make_uint4(dv[0], dv[1], dv[2], dv[3]));
-        } else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-            if (vq + c < V) row[c] = dv[c];
-        }
-      }
-    }
-    __syncthreads();  // s_T is rewritten by the next half
-  }
-  if (a.digest) {
-    // 16 roots x 64 lanes -> lane (32 a + 16 b + 8 c + 4 d) holds root 8a+4b+2c+d
-    xreduce_step<16>(pk, q, 32);
-    xreduce_step<8>(pk, q, 16);
-    xreduce_step<4>(pk, q, 8);
-    xreduce_step<2>(pk, q, 4);
-    xreduce_step<16>(hh, q, 32);
-    xreduce_step<8>(hh, q, 16);
-    xreduce_step<4>(hh, q, 8);
-    xreduce_step<2>(hh, q, 4);
-    uint32_t p = pk[0];
-    uint64_t h = hh[0];
-#pragma unroll
-    for (int o = 2; o > 0; o >>= 1) {
-      p += (uint32_t)__shfl_xor((int)p, o);
-      h += shfl_xor64(h, o);
-    }
-    const uint32_t r = 16u * rg + ((q >> 5) & 1u) * 8u + ((q >> 4) & 1u) * 4u +
-                       ((q >> 3) & 1u) * 2u + ((q >> 2) & 1u);
-    if ((q & 3u) == 0 && r < nr && (p & 0xFFFFu)) {
-      ospf_digest* dg = a.digest + b.rix0 + r;
-      atomicAdd((unsigned long long*)&dg->reached, (unsigned long long)(p & 0xFFFFu));
-      atomicAdd((unsigned long long*)&dg->sum_dist, (unsigned long long)(p >> 16));
-      atomicAdd((unsigned long long*)&dg->hash, (unsigned long long)h);
-    }
-  }
-}
-
 // Phase 2: block = (group of G roots, chunk of C node tiles); a tile is
 // T = 1024 / S nodes, S threads per node quad splitting a root's next-hop
 // words. The group's neighbour tables (level row per usable transit
@@ -1811,7 +1662,7 @@ __global__ void __launch_bounds__(256) nh_wide_plan_kernel(DevGraph g, WidePlan 
     const uint32_t nq = v0 + 4u * wave;
     uint64_t kn[4] = {0ull, 0ull, 0ull, 0ull};
     uint32_t Lmine = 0u;
-    if (nq < V && !d.late_keys) {
+    if (nq < V) {
 #pragma unroll
       for (int b = 0; b < 4; ++b) kn[b] = d.digest ? g.dkn[nq + b] : 0ull;  // zero past V
       Lmine = lane < ng ? *reinterpret_cast<const uint32_t*>(d.lev + (size_t)s_own[lane] * d.pitch + nq) : 0u;
@@ -1838,16 +1689,12 @@ __global__ void __launch_bounds__(256) nh_wide_plan_kernel(DevGraph g, WidePlan 
     }
     __syncthreads();
     if (nq >= V) continue;  // wave-uniform (the next barrier is reached by all)
-    if (d.late_keys) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) kn[b] = d.digest ? g.dkn[nq + b] : 0ull;
-      Lmine = lane < ng ? *reinterpret_cast<const uint32_t*>(d.lev + (size_t)s_own[lane] * d.pitch + nq) : 0u;
-    }
     // (Lmine: lane j holds root j's own levels at the 4 nodes)
     // st16 (wave-uniform): the 4 records (4 W words, 7 whole 128-B lines at
     // W = 56) staged in LDS and stored as W 16-B pieces by one instruction,
-    // instead of 4 stores of W words whose 128-B lines straddle them
-    const bool st16 = d.st16 && (W & 3u) == 0 && nq + 4u <= V;
+    // instead of 4 stores of W words whose 128-B lines straddle them (19.74 ->
+    // 19.21 ms per F100k sweep in one process, profiles/r06/l1_late_kernel_ab.txt)
+    const bool st16 = (W & 3u) == 0 && nq + 4u <= V;
     uint32_t* rec = reinterpret_cast<uint32_t*>(s_rec[wave]);
     uint32_t word[4] = {0u, 0u, 0u, 0u}, Lp = 0xFFFFFFFFu;
     // the word key of each node's masked word, kept while the next root's
@@ -2127,28 +1974,12 @@ hipError_t launch_msbfs_round(int kp, const DevGraph& g, const MsArgs& a, uint32
   }
 }
 
-hipError_t launch_msbfs_levels(const DevGraph& g, const MsArgs& a, uint32_t depth_bound,
-                               hipStream_t s) {
-  const uint32_t init_blocks = (a.nb * a.R + kWavesPerBlock - 1) / kWavesPerBlock;
-  hipLaunchKernelGGL(msbfs_init_kernel<-1>, dim3(init_blocks), dim3(kBlock), 0, s, g, a);
-  const uint32_t chunks = (g.V + kBlock - 1) / kBlock;
-  const uint32_t bigblocks = (g.nbig + kWavesPerBlock - 1) / kWavesPerBlock;
-  for (uint32_t d = 1; d <= depth_bound; ++d) {
-    hipLaunchKernelGGL(msbfs_level_kernel<-1>, dim3(a.nb * (chunks + bigblocks)), dim3(kBlock), 0,
-                       s, g, a, d);
-    hipLaunchKernelGGL(msbfs_settle_kernel<-1>, dim3(a.nb * chunks), dim3(kBlock), 0, s, g, a, d);
-  }
-  hipLaunchKernelGGL(msbfs_levrows_kernel, dim3(a.nb * ((g.V + 511u) / 512u)), dim3(kBlock), 0, s,
-                     g, a);
-  return hipGetLastError();
-}
-
 hipError_t launch_nh_derive(const DevGraph& g, const DeriveArgs& d0, hipStream_t s) {
   DeriveArgs d = d0;
   if (d.n == 0) return hipSuccess;
   if (d.W == 0 || d.W > kDeriveTab / 32u || d.cap == 0 || d.cap > kDeriveTab)
     return hipErrorInvalidValue;
-  if (d.W <= 4 && !getenv("OSPF_DERIVE_QUAD")) {  // lane = 16 nodes, words in registers
+  if (d.W <= 4 && !knob_flag(Knob::OSPF_DERIVE_QUAD)) {  // lane = 16 nodes, words in registers
     d.G = std::max<uint32_t>(1, std::min<uint32_t>(kDeriveMaxG, kDeriveTab / d.cap));
     d.tiles = (g.V + 1023u) / 1024u;
     // 16 tiles per block: measured at F100k, W = 1 10.98 -> 10.08 ms, W = 3
@@ -2165,10 +1996,8 @@ hipError_t launch_nh_derive(const DevGraph& g, const DeriveArgs& d0, hipStream_t
     }
     return hipGetLastError();
   }
-  if (d.W > 4 && !getenv("OSPF_DERIVE_GENERIC")) {  // runs of equal lists share the words
-    d.G = kWideG;
-    if (const char* e = getenv("OSPF_DERIVE_WIDE_G"))
-      d.G = std::max<uint32_t>(1, std::min<uint32_t>(kWideG, (uint32_t)atoi(e)));
+  if (d.W > 4 && !knob_flag(Knob::OSPF_DERIVE_GENERIC)) {  // runs of equal lists share the words
+    d.G = (uint32_t)knob_int(Knob::OSPF_DERIVE_WIDE_G);
     d.tiles = (g.V + kWideTile - 1) / kWideTile;
     d.ctiles = std::max<uint32_t>(1, std::min<uint32_t>(d.tiles, d.ctiles ? d.ctiles : 2));
     d.chunks = (d.tiles + d.ctiles - 1) / d.ctiles;
@@ -2194,19 +2023,10 @@ hipError_t launch_nh_derive(const DevGraph& g, const DeriveArgs& d0, hipStream_t
 hipError_t launch_wide_plan(const DevGraph& g, const WidePlan& p0, hipStream_t s) {
   WidePlan p = p0;
   if (p.n == 0) return hipSuccess;
-  // digest keys and own levels issued with the slot loads (OSPF_WIDE_LATE_KEYS:
-  // after the tile's barrier, as before; read per launch for in-process A/B)
-  p.late_keys = getenv("OSPF_WIDE_LATE_KEYS") ? 1u : 0u;
-  // records staged in LDS, 16-B stores (OSPF_WIDE_ST16=0: 4 word stores per
-  // wave and root, as before; read per launch): 19.74 -> 19.21 ms per F100k
-  // sweep in one process, profiles/r06/l1_late_kernel_ab.txt (box 3)
-  const char* se = getenv("OSPF_WIDE_ST16");
-  p.st16 = (!se || atoi(se) != 0) ? 1u : 0u;
   if (p.W < 1 || p.W > 64 || p.pitch % kW3Tile) return hipErrorInvalidValue;
   p.tiles = (g.V + kW3Tile - 1) / kW3Tile;
   // ~4096 blocks; a chunk of >= 7 tiles covers a 128-B line of every row
-  const char* we = getenv("OSPF_WIDE_BLOCKS");  // read per launch: in-process A/B
-  const uint32_t want = we ? (uint32_t)std::max(1, atoi(we)) : 8192u;  // (4096: +0.05 ms at F100k)
+  const uint32_t want = (uint32_t)knob_int(Knob::OSPF_WIDE_BLOCKS);  // (4096: +0.05 ms at F100k)
   if (!p.ctiles) p.ctiles = std::max<uint32_t>(7, p.tiles / std::max<uint32_t>(1, want / p.nruns));
   p.ctiles = std::min(p.ctiles, p.tiles);
   p.chunks = (p.tiles + p.ctiles - 1) / p.ctiles;

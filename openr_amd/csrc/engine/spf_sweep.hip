@@ -109,7 +109,7 @@ void par_stable_sort(std::vector<T>& v, Less less) {
 // OSPF_SWEEP_TIMING: sub-phases of a plan phase on stderr
 struct SubLaps {
   const char* phase;
-  bool on = getenv("OSPF_SWEEP_TIMING") != nullptr;
+  bool on = knob_flag(Knob::OSPF_SWEEP_TIMING);
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   explicit SubLaps(const char* p) : phase(p) {}
   void operator()(const char* what) {
@@ -348,7 +348,7 @@ int new_event(ospf_sweep* s) {
 // 16-B store path); OSPF_SWEEP_ROW_PITCH=V keeps the packed pitch (A/B knob)
 uint32_t row_pitch(uint32_t V) {
   if (V & 3u) return V;
-  if (const char* e = getenv("OSPF_SWEEP_ROW_PITCH"))
+  if (const char* e = knob_str(Knob::OSPF_SWEEP_ROW_PITCH))
     if (e[0] == 'V') return V;
   return (V + 31u) / 32u * 32u;
 }
@@ -799,7 +799,7 @@ int hub_build(ospf_ctx* c, const Facts& f, const std::vector<uint32_t>& roots, u
 //     on their own streams beside (B).
 // OSPF_SWEEP_TIMING: host phases of a plan on stderr
 struct PlanLaps {
-  bool on = getenv("OSPF_SWEEP_TIMING") != nullptr;
+  bool on = knob_flag(Knob::OSPF_SWEEP_TIMING);
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   void operator()(const char* what) {
     if (!on) return;
@@ -815,10 +815,8 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   const uint32_t V = s->V;
   const uint32_t hop = s->opts.flags & OSPF_HOP_COUNT;
   PlanLaps lap;
-  double leaf_tail = 0.0;
-  if (const char* x = getenv("OSPF_SWEEP_LEAF_TAIL")) leaf_tail = std::max(0.0, std::min(0.9, atof(x)));
   std::vector<uint8_t> leaf;
-  if (!getenv("OSPF_SWEEP_NOLEAF")) leaf = leaf_set(f);
+  if (!knob_flag(Knob::OSPF_SWEEP_NOLEAF)) leaf = leaf_set(f);
   else leaf.assign(V, 0);
   lap("leaf set");
   std::vector<uint32_t> own_l, own_c;
@@ -857,7 +855,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   // so can a cover row (twin levels)
   lap("width classes");
   Twins tw;
-  if (!getenv("OSPF_SWEEP_NOTWIN")) tw = twin_classes(c);
+  if (!knob_flag(Knob::OSPF_SWEEP_NOTWIN)) tw = twin_classes(c);
   lap("twin classes");
   // classes of r's usable transit neighbours (sorted, unique); false past
   // kTwinMaxC. Every node's, once, on host threads: [V][kTwinMaxC + 1] slots
@@ -898,14 +896,14 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
       classes += cs.size();
     }
     // worth it when a class covers several slots (OSPF_SWEEP_TWIN=1: always)
-    return getenv("OSPF_SWEEP_TWIN") || slots >= 3 * std::max<uint64_t>(1, classes);
+    return knob_flag(Knob::OSPF_SWEEP_TWIN) || slots >= 3 * std::max<uint64_t>(1, classes);
   };
   bool all_leaf_rows = false;  // a class reads every neighbour's row (not twins)
   for (auto& k : cls) {
     k.twin = k.W <= 4 && !tw.cls.empty() && twin_ok(k.roots);
     if (k.reads_leaf && !k.twin) all_leaf_rows = true;
   }
-  all_leaf_rows |= tw.cls.empty() || getenv("OSPF_SWEEP_ALL_LEAF_ROWS") != nullptr;
+  all_leaf_rows |= tw.cls.empty() || knob_flag(Knob::OSPF_SWEEP_ALL_LEAF_ROWS);
   lap("twin width classes");
   std::vector<uint32_t> need_l = own_l;
   need_l.insert(need_l.end(), extra_l.begin(), extra_l.end());
@@ -922,7 +920,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   // are BFS rows (a derived representative leaves the set: repeat until
   // stable), and so are the leaf representatives the twin next hops read
   std::vector<uint8_t> in_d(V, 0), seed(V, 0);
-  bool twin_lv = !tw.cls.empty() && !getenv("OSPF_SWEEP_NOTWINLV");
+  bool twin_lv = !tw.cls.empty() && !knob_flag(Knob::OSPF_SWEEP_NOTWINLV);
   if (twin_lv) {
     for (uint32_t v = 0; v < V; ++v)
       if (in_a[v] && f.nbrs(v) <= 128 && classes_of(v)) in_d[v] = 1;
@@ -951,7 +949,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
     uint32_t nbfs = 0;
     for (uint32_t v = 0; v < V; ++v) nbfs += (in_a[v] && !in_d[v]) || seed[v];
     // worth it when the traversal shrinks to half (OSPF_SWEEP_TWINLV=1: always)
-    if (!getenv("OSPF_SWEEP_TWINLV") && 2ull * nbfs > n_cover) twin_lv = false;
+    if (!knob_flag(Knob::OSPF_SWEEP_TWINLV) && 2ull * nbfs > n_cover) twin_lv = false;
     if (!twin_lv) {
       std::fill(in_d.begin(), in_d.end(), 0);
       std::fill(seed.begin(), seed.end(), 0);
@@ -966,7 +964,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   // (OSPF_SWEEP_MERGE_REPS: the BFS'd leaf representatives' next hops in
   // their groups' leaf launch -- rows re-derived there, identical -- instead
   // of a launch of their own that reads each one's neighbour rows alone)
-  const bool merge_reps = twin_lv && getenv("OSPF_SWEEP_MERGE_REPS") != nullptr;
+  const bool merge_reps = twin_lv && knob_flag(Knob::OSPF_SWEEP_MERGE_REPS);
   std::vector<uint32_t> reps, rest;
   for (uint32_t x : need_l) {
     const bool first = twin_lv ? (seed[x] != 0 && !merge_reps)
@@ -996,8 +994,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   // switches) reading <= kTwinMaxC class rows together (OSPF_TWIN_LV_G=4:
   // <= 4 rows, the launch's 4-root kernel with half the per-root registers)
   std::vector<uint32_t> dgo{0u};
-  const char* tge = getenv("OSPF_TWIN_LV_G");
-  const uint32_t tlg = tge && atoi(tge) == 4 ? 4u : ospf::kTwinLvG;
+  const uint32_t tlg = knob_int(Knob::OSPF_TWIN_LV_G) == 4 ? 4u : ospf::kTwinLvG;
   if (nd) {
     std::vector<uint32_t> cl;
     for (uint32_t i = 0; i < nd; ++i) {
@@ -1024,7 +1021,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   uint32_t S = 0;
   if (nd) {
     S = 1;
-    if (const char* e = getenv("OSPF_SWEEP_STAGES")) S = (uint32_t)std::max(1, atoi(e));
+    S = (uint32_t)knob_int(Knob::OSPF_SWEEP_STAGES, (int)S);
     S = std::min(S, n_dgrp);
   }
   std::vector<uint32_t> sg(S + 1, 0u);  // first group of each stage
@@ -1130,9 +1127,8 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
     s->units.push_back(lv);
   }
   // the twin next-hop launches write their roots' dist rows (from the level
-  // rows they read anyway), off the serial prefix (OSPF_TWIN_DIST_IN_LEVELS:
-  // the twin levels write them, as before)
-  const bool nh_dist = twin_lv && !getenv("OSPF_TWIN_DIST_IN_LEVELS");
+  // rows they read anyway), off the serial prefix
+  const bool nh_dist = twin_lv;
   std::vector<uint8_t> twin_nh(V, 0);
   for (const auto& k : cls)
     if (k.twin)
@@ -1200,7 +1196,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
       });
     const uint32_t n = (uint32_t)k.roots.size(), W = k.W, cap = std::min(k.cap, 2048u);
     uint32_t *d_roots, *nh;
-    // twin classes' next-hop rows 128-B aligned too (nh_derive_twin_kernel
+    // twin classes' next-hop rows 128-B aligned too (nh_twin4_kernel
     // stores each 1,024-node tile's W words as one run)
     const uint32_t NPW = k.twin ? row_pitch(V * W) : V * W;
     if ((rc = upload(s, &d_roots, k.roots)) || (rc = dalloc(s, &nh, (size_t)n * NPW))) return rc;
@@ -1219,7 +1215,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
         if (a1 == a0) continue;
         ospf_sweep::Unit u;
         u.name = "derive_cap" + std::to_string(k.cap) + "_s" + std::to_string(q);
-        u.kernel = "ospf_nh_derive_twin_dev (nh_derive_twin_kernel, " + std::to_string(W) +
+        u.kernel = "ospf_nh_derive_twin_dev (nh_twin4_kernel, " + std::to_string(W) +
                    " next-hop word" + (W > 1 ? "s)" : ")");
         u.stream = st;
         u.wait = {ev_s[q]};
@@ -1241,7 +1237,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
       }
       continue;
     }
-    if (!k.twin && W > 4 && W <= 64 && !getenv("OSPF_DERIVE_WIDE1")) {
+    if (!k.twin && W > 4 && W <= 64 && !knob_flag(Knob::OSPF_DERIVE_WIDE1)) {
       // spines: the planned tile-staged kernel (host-built runs and slot tables)
       WideHost wh;
       if ((rc = wide_plan_build(c, f, k.roots, W, pos, wh))) return sfail(s, rc, c->err);
@@ -1286,7 +1282,7 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
     ospf_sweep::Unit u;
     u.name = "derive_cap" + std::to_string(k.cap);
     u.kernel = std::string(k.twin ? "ospf_nh_derive_twin_dev (" : "ospf_nh_derive_dev (") +
-               (k.twin ? "nh_derive_twin_kernel" : W <= 4 ? "nh_derive16_kernel"
+               (k.twin ? "nh_twin4_kernel" : W <= 4 ? "nh_derive16_kernel"
                                                           : "nh_derive_wide_kernel") +
                ", " + std::to_string(W) + " next-hop word" + (W > 1 ? "s)" : ")");
     u.stream = st;
@@ -1382,55 +1378,6 @@ int plan_derive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
         const uint32_t ngq = g1 - g0;
         u.fn = [=](hipStream_t strm) {
           return ospf_int::leaf_derive(c, dl, n, d_gq, ngq, kmax, lev, pitch, d_pos, lo, dist, DP, nh,
-                                       DP, dg2, strm);
-        };
-        s->step_comp += u.comp;
-        s->units.push_back(std::move(u));
-      }
-    } else if (nL > nR && leaf_tail > 0.0 && twin_lv && ngr >= 2) {
-      // the leaves in two launches on the main stream: the second waits for
-      // the largest cover next-hop launch, which so gets the GPU's share
-      // before it and no longer finishes alone after the leaves
-      // (OSPF_SWEEP_LEAF_TAIL = the second launch's share of the groups)
-      int big = -1;
-      for (size_t x = 0; x < s->units.size(); ++x)
-        if (s->units[x].name.rfind("derive_cap", 0) == 0 && s->units[x].record < 0 &&
-            (big < 0 || s->units[x].comp > s->units[big].comp))
-          big = (int)x;
-      const uint32_t gs = std::min(ngr - 1, std::max(1u, ngr - (uint32_t)(ngr * leaf_tail)));
-      int ev_tn = -1;
-      if (big >= 0) {
-        ev_tn = new_event(s);
-        if (ev_tn < 0) return ev_tn;
-        s->units[big].record = ev_tn;
-      }
-      std::vector<uint32_t> gq;
-      for (uint32_t g = gs; g <= ngr; ++g) gq.push_back(grp[g] - grp[gs]);
-      uint32_t* d_gq;
-      if ((rc = upload(s, &d_gq, gq))) return rc;
-      const uint32_t* lo = drop_rest ? d_lout : nullptr;
-      for (int part = 0; part < 2; ++part) {
-        ospf_sweep::Unit u;
-        u.name = part ? "leaf_tail" : "leaf";
-        u.kernel = "ospf_leaf_derive2_dev (leaf_derive_kernel: level + dist + next-hop rows of leaf "
-                   "roots from their neighbours' level rows)";
-        u.stream = 0;
-        const uint32_t i0 = part ? grp[gs] : 0u, i1 = part ? grp[ngr] : grp[gs];
-        const uint32_t n = i1 - i0, ngq = part ? ngr - gs : gs;
-        if (part) {
-          if (ev_tn >= 0) u.wait = {ev_tn};
-          u.record = ev_b;
-        }
-        u.n_roots = n;
-        u.W = 1;
-        u.comp = (uint64_t)n * 8ull * V;
-        const uint32_t* dl = d_l + nR + i0;
-        uint32_t* nh = lnh + (size_t)(nR + i0) * DP;
-        ospf_digest* dg2 = dg + nR + i0;
-        const uint32_t* lo2 = lo ? lo + i0 : nullptr;
-        const uint32_t* gp = part ? d_gq : d_grp;
-        u.fn = [=](hipStream_t strm) {
-          return ospf_int::leaf_derive(c, dl, n, gp, ngq, kmax, lev, pitch, d_pos, lo2, dist, DP, nh,
                                        DP, dg2, strm);
         };
         s->step_comp += u.comp;
@@ -1716,7 +1663,7 @@ int plan_wcover(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   // rows unit and no neighbour-row derivation runs for them.
   std::vector<uint32_t> seeds, clos;
   ospf_int::ClosureHost ch;
-  bool closure = !c->cl_seed.empty() && !getenv("OSPF_COVER_NOCLOSURE");
+  bool closure = !c->cl_seed.empty() && !knob_flag(Knob::OSPF_COVER_NOCLOSURE);
   uint32_t NW = 0;
   if (closure) {
     const uint32_t nS = (uint32_t)c->h_ccv.size();
@@ -1733,7 +1680,7 @@ int plan_wcover(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
     NW = clos.empty() ? 0u : f.words(clos[0]);
     for (uint32_t r : clos)
       if (f.words(r) != NW) NW = 0;
-    if (NW > ospf::kClMaxNW || getenv("OSPF_CLOSURE_NONH")) NW = 0;
+    if (NW > ospf::kClMaxNW || knob_flag(Knob::OSPF_CLOSURE_NONH)) NW = 0;
     closure = clos.size() >= seeds.size() && ospf_int::closure_build(c, clos, seed_row, ch, NW) == OSPF_OK;
     if (!closure && NW) {  // the masks do not apply: distances only
       NW = 0;
@@ -1752,7 +1699,7 @@ int plan_wcover(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   // Dial, rows + digests after it (cover_spf_kernel seed mode)
   std::vector<uint32_t> sd_nh;
   uint32_t NWs = 0;
-  if (closure && !getenv("OSPF_SEED_NONH")) {
+  if (closure && !knob_flag(Knob::OSPF_SEED_NONH)) {
     std::vector<uint8_t> in_d(V, 0);
     for (uint32_t r : c_der) in_d[r] = 1;
     for (uint32_t r : seeds)
@@ -1835,7 +1782,7 @@ int plan_wcover(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   // the Dial over the contracted cover graph: the seeds' rows (closure) or
   // every cover row
   s->trav_edges = (uint64_t)(closure ? seeds.size() : nA) * c->h_cedge.size();
-  if (getenv("OSPF_SWEEP_DEBUG"))
+  if (knob_flag(Knob::OSPF_SWEEP_DEBUG))
     fprintf(stderr, "plan_wcover: cover %u seeds %zu comps %zu closure roots %zu -> %s (%s)\n", nA,
             c->cl_seed.size(), c->cl_comp_off.size() - 1, clos.size(), closure ? "closure" : "dial",
             c->err.c_str());
@@ -1895,7 +1842,7 @@ int plan_wcover(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
     ospf_digest* sdg = nullptr;
     // the seeds' rows on a stream of their own, beside the closure and its
     // rows (OSPF_SEED_ROWS_INLINE: inside the Dial's launch)
-    const bool seed_side = nsn && !getenv("OSPF_SEED_ROWS_INLINE");
+    const bool seed_side = nsn && !knob_flag(Knob::OSPF_SEED_ROWS_INLINE);
     if (nsn) {
       std::vector<uint32_t> snp(nsd, kNone), at(V, kNone), srp2(nsn);
       for (uint32_t k = 0; k < nsn; ++k) {
@@ -2002,14 +1949,14 @@ int plan_wcover(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
     // rows of the chunks done run beside the next chunk. Measured slower on
     // the weighted F100k (58.5 vs 54.9 ms, a22): the bandwidth-bound leaf
     // launch takes the CUs the latency-bound rows launch needs.
-    const uint32_t K = (nL && ncl >= 64 && getenv("OSPF_WCOVER_STAGE")) ? 4u : 1u;
+    const uint32_t K = (nL && ncl >= 64 && knob_flag(Knob::OSPF_WCOVER_STAGE)) ? 4u : 1u;
     // opt-in (OSPF_COVER_ROWS_TILED): with next hops, the rows by node tiles x
     // root chunks (closure_tile_rows_kernel) instead of a node-order pass per
     // root; exact, but measured 2x slower on the weighted F100k (35.3 vs
     // 16.9 ms, a27 / a28)
     bool tiled = false;
     ospf::ClosureRowsPlan rp{};
-    if (cl_nh && K == 1 && getenv("OSPF_COVER_ROWS_TILED")) {
+    if (cl_nh && K == 1 && knob_flag(Knob::OSPF_COVER_ROWS_TILED)) {
       NodeTiles nt;
       tiled = node_tiles(c, nt) && !nt.tile.empty();
       if (tiled) {
@@ -2127,7 +2074,7 @@ int plan_wcover(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
     };
     HubHost hh;
     const std::string err0 = c->err;
-    const bool hub = W <= 4 && getenv("OSPF_WNH_HUB") && hub_build(c, f, roots, W, pos, hh) == OSPF_OK;
+    const bool hub = W <= 4 && knob_flag(Knob::OSPF_WNH_HUB) && hub_build(c, f, roots, W, pos, hh) == OSPF_OK;
     if (!hub) c->err = err0;  // not applicable: the lanes / wide kernels run
     if (hub) {
       uint4* d_grp;
@@ -2170,7 +2117,7 @@ int plan_wcover(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
     }
     WRunsHost wh;
     const std::string err1 = c->err;
-    const bool runs = W > 4 && getenv("OSPF_WNH_RUNS") && wruns_build(c, f, roots, W, pos, wh) == OSPF_OK;
+    const bool runs = W > 4 && knob_flag(Knob::OSPF_WNH_RUNS) && wruns_build(c, f, roots, W, pos, wh) == OSPF_OK;
     if (!runs) c->err = err1;
     if (runs) {  // runs of roots with one neighbour list
       uint4* d_run;
@@ -2335,11 +2282,10 @@ int plan_wmulti(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   for (uint32_t j = 0; j < nL; ++j) pos[own_l[j]] = nS + j;
   // concurrent groups: two per CU, within a scratch budget (OSPF_MSD_MB, 64 GB)
   const uint32_t ngroups = (nS + 31u) / 32u;
-  size_t budget = 65536ull << 20;
-  if (const char* e = getenv("OSPF_MSD_MB")) budget = (size_t)std::max(64, atoi(e)) << 20;
+  size_t budget = (size_t)knob_int(Knob::OSPF_MSD_MB) << 20;
   const size_t per = ospf::msdist_scratch_bytes(V, 1);
   uint32_t delta = hop ? 1u : std::max<uint32_t>(1, c->info.max_metric);
-  if (const char* e = getenv("OSPF_MSD_DELTA")) delta = (uint32_t)std::max(1, atoi(e));
+  delta = (uint32_t)knob_int(Knob::OSPF_MSD_DELTA, (int)delta);
   uint32_t *slab, *d_pos, *d_s, *d_l, *lnh, *scratch = nullptr;
   int rc;
   if ((rc = dalloc(s, &slab, (size_t)(nS + nL) * V)) || (rc = upload(s, &d_pos, pos)) ||
@@ -2361,7 +2307,7 @@ int plan_wmulti(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
   }
   uint32_t blocks = std::min<uint32_t>(std::max(1u, ngroups), 2u * (uint32_t)c->n_cu);
   blocks = std::max<uint32_t>(1, std::min<uint32_t>(blocks, (uint32_t)(budget / per)));
-  if (const char* e = getenv("OSPF_MSD_BLOCKS")) blocks = std::max(1, std::min((int)blocks, atoi(e)));
+  blocks = std::min(blocks, (uint32_t)knob_int(Knob::OSPF_MSD_BLOCKS, (int)blocks));
   for (;;) {
     if (dalloc_try(s, &scratch, per * blocks / sizeof(uint32_t)) == OSPF_OK) break;
     if (blocks == 1) return sfail(s, OSPF_E_NOMEM, "wmulti: no room for one traversal's scratch");
@@ -2395,7 +2341,7 @@ int plan_wmulti(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& mine
       a.dist = slab;
       a.pitch = V;
       a.scratch = scratch;
-      const bool dbg = getenv("OSPF_MSD_STATS") != nullptr;
+      const bool dbg = knob_flag(Knob::OSPF_MSD_STATS);
       unsigned long long* st = nullptr;
       if (dbg && (hipMalloc(&st, 32) != hipSuccess || hipMemset(st, 0, 32) != hipSuccess))
         return ospf_int::fail(c, OSPF_E_DEVICE, "msdist stats");
@@ -2652,7 +2598,7 @@ int run_eager(ospf_sweep* s, hipStream_t caller) {
 // identically), the faster kept for the HIP graph and every later run.
 // OSPF_LEAF_GROUP_MAJOR fixes the order; OSPF_LEAF_NO_AUTO keeps chunk-major.
 int pick_leaf_order(ospf_sweep* s) {
-  if (getenv("OSPF_LEAF_GROUP_MAJOR") || getenv("OSPF_LEAF_NO_AUTO")) return OSPF_OK;
+  if (knob_set(Knob::OSPF_LEAF_GROUP_MAJOR) || knob_flag(Knob::OSPF_LEAF_NO_AUTO)) return OSPF_OK;
   ospf_sweep::Unit* u = nullptr;
   for (auto& x : s->units)
     if (x.name == "leaf") u = &x;
@@ -2677,7 +2623,7 @@ int pick_leaf_order(ospf_sweep* s) {
   hipEventDestroy(b);
   if (rc) return sfail(s, rc, "sweep: leaf order probe: " + std::string(ospf_last_error(s->c)));
   s->leaf_order = best[1] < best[0] ? 1 : 0;
-  if (getenv("OSPF_SWEEP_TIMING"))
+  if (knob_flag(Knob::OSPF_SWEEP_TIMING))
     fprintf(stderr, "sweep_create leaf order %s (chunk-major %.3f ms, group-major %.3f ms)\n",
             s->leaf_order ? "group-major" : "chunk-major", best[0], best[1]);
   return ospf_sync(s->c, st);
@@ -2760,7 +2706,7 @@ int ospf_sweep_create(ospf_ctx* c, const ospf_sweep_opts* o, ospf_sweep** out) {
     x->c = nullptr;
   };
   s->opts = *o;
-  s->early = (o->flags & OSPF_SWEEP_EARLY_START) && !getenv("OSPF_SWEEP_NO_EARLY");
+  s->early = (o->flags & OSPF_SWEEP_EARLY_START) && !knob_flag(Knob::OSPF_SWEEP_NO_EARLY);
   s->gen = c->graph_gen;
   s->V = c->info.n_nodes;
   const uint32_t V = s->V;
@@ -2776,7 +2722,7 @@ int ospf_sweep_create(ospf_ctx* c, const ospf_sweep_opts* o, ospf_sweep** out) {
     c->err = m;
     return rc;
   };
-  const bool tm = getenv("OSPF_SWEEP_TIMING") != nullptr;
+  const bool tm = knob_flag(Knob::OSPF_SWEEP_TIMING);
   auto t0 = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!tm) return;
@@ -2801,7 +2747,7 @@ int ospf_sweep_create(ospf_ctx* c, const ospf_sweep_opts* o, ospf_sweep** out) {
   // small graphs: every root's next hops in <= 4 words and the graph in LDS
   const uint32_t max_w = std::max(1u, (c->max_dn + 31) / 32);
   const bool lds_ok = unit && max_w <= 4 && ospf_lds_sweep_fits(c, o->flags & OSPF_HOP_COUNT, max_w) &&
-                      !getenv("OSPF_SWEEP_NOLDS");
+                      !knob_flag(Knob::OSPF_SWEEP_NOLDS);
   std::vector<uint8_t> leaf;
   bool any_leaf = false;
   uint32_t mode = o->mode;
@@ -2872,7 +2818,7 @@ int ospf_sweep_create(ospf_ctx* c, const ospf_sweep_opts* o, ospf_sweep** out) {
   // bit 8 in the rows kernel) instead of the transit-depth bound (10 at
   // F100k, where the seeds' BFS ends at 4: 14 empty level launches).
   // OSPF_SWEEP_FULL_DEPTH keeps the bound.
-  if (s->d_lv_maxd && !getenv("OSPF_SWEEP_FULL_DEPTH")) {
+  if (s->d_lv_maxd && !knob_flag(Knob::OSPF_SWEEP_FULL_DEPTH)) {
     uint32_t dm = 0;
     if (hipMemcpy(&dm, s->d_lv_maxd, 4, hipMemcpyDeviceToHost) != hipSuccess)
       return bail(fail(c, OSPF_E_DEVICE, "sweep: seed BFS depth readback"));
@@ -3168,7 +3114,7 @@ namespace {
 bool multi_rccl(ospf_multi* m) {
   if (m->rccl) return m->rccl > 0;
   m->rccl = -1;
-  const char* e = getenv("OSPF_RCCL");
+  const char* e = knob_str(Knob::OSPF_RCCL);
   if (e && e[0] == '0') return false;
   const size_t n = m->ctx.size();
   std::vector<int> devs;

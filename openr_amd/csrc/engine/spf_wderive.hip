@@ -437,7 +437,7 @@ __global__ void __launch_bounds__(256) wderive_wide_kernel(DevGraph g, WDeriveAr
 
 // Cover roots with more than 128 neighbours (W > 4 words: the spines of a
 // fabric, whose neighbours are one switch per pod). Lane = next-hop word w
-// (slots 32 w .. 32 w + 31), a wave walks 2-node chunks of the block's tile;
+// (slots 32 w .. 32 w + 31), a wave walks 4-node chunks of the block's tile;
 // a run of consecutive roots with the same neighbour list (the spines of one
 // plane) loads each chunk's slot values once and every root of the run adds
 // its own link metrics (u16 in LDS) and compares with its own row (staged per
@@ -449,8 +449,10 @@ constexpr uint32_t kWlTile = 256;
 // its slots 32 w + i at i * 64 + w, consecutive lanes consecutive u16s (the
 // k-major table put every lane of a read on two banks)
 __device__ __forceinline__ uint32_t widx(uint32_t k) { return (k & 31u) * 64u + (k >> 5); }
-template <uint32_t NC>  // nodes per chunk: 2 (8-B loads) or 4 (16-B loads)
 __global__ void __launch_bounds__(256) wderive_lanes_kernel(DevGraph g, WDeriveArgs a) {
+  // nodes per chunk (16-B loads of each slot row): F100k-w spines 71 -> 40 ms
+  // in the sweep against 2 nodes (8-B loads)
+  constexpr uint32_t NC = 4;
   __shared__ uint32_t s_pos[kWlK];
   __shared__ uint16_t s_w[kWlG][kWlK];
   __shared__ uint32_t s_R[kWlG][kWlTile];
@@ -568,17 +570,11 @@ __global__ void __launch_bounds__(256) wderive_lanes_kernel(DevGraph g, WDeriveA
           if (p < kNt) {
             const uint32_t* row = a.src + (size_t)p * a.src_pitch + vc;
             if (a.vec && vc + NC - 1u < V) {
-              if constexpr (NC == 4) {
-                const uint4 x = *reinterpret_cast<const uint4*>(row);
-                D[0][i] = x.x;
-                D[1][i] = x.y;
-                D[2][i] = x.z;
-                D[3][i] = x.w;
-              } else {
-                const uint2 x = *reinterpret_cast<const uint2*>(row);
-                D[0][i] = x.x;
-                D[1][i] = x.y;
-              }
+              const uint4 x = *reinterpret_cast<const uint4*>(row);
+              D[0][i] = x.x;
+              D[1][i] = x.y;
+              D[2][i] = x.z;
+              D[3][i] = x.w;
             } else {
 #pragma unroll
               for (uint32_t n = 0; n < NC; ++n) D[n][i] = vc + n < V ? row[n] : kInf;
@@ -933,11 +929,7 @@ hipError_t launch_wderive_wide(const DevGraph& g, WDeriveArgs a, uint32_t W, hip
     a.ctiles = std::min(a.ctiles, a.tiles);
     a.chunks = (a.tiles + a.ctiles - 1) / a.ctiles;
     const dim3 grid(((a.n + kWlG - 1) / kWlG) * a.chunks);
-    // 4 nodes per chunk (16-B loads of each slot row): F100k-w spines 71 -> 40
-    // ms in the sweep (OSPF_WL_NC=2: the 8-B form)
-    const char* nc = getenv("OSPF_WL_NC");
-    if (nc && atoi(nc) == 2) hipLaunchKernelGGL(wderive_lanes_kernel<2>, grid, dim3(kBlock), 0, s, g, a);
-    else hipLaunchKernelGGL(wderive_lanes_kernel<4>, grid, dim3(kBlock), 0, s, g, a);
+    hipLaunchKernelGGL(wderive_lanes_kernel, grid, dim3(kBlock), 0, s, g, a);
     return hipGetLastError();
   }
   a.tiles = (g.V + kSub - 1) / kSub;

@@ -85,7 +85,6 @@ def main():
         return
     envs = {"base": ({}, 1), "graphoff": ({}, 0), "seednonh": ({"OSPF_SEED_NONH": "1"}, 1),
             "closurenonh": ({"OSPF_CLOSURE_NONH": "1"}, 1),
-            "zerok": ({"OSPF_ZERO_KERNEL": "1"}, 1),
             "memset": ({"OSPF_ZERO_MEMSET": "1"}, 1), "memsetoff": ({"OSPF_ZERO_MEMSET": "1"}, 0), "nopoison": ({"RP_NOPOISON": "1"}, 1)}
     for v in a.variants.split(","):
         e, g = envs[v]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time one root class of the F100k all-sources sweep in isolation (one
 stream, back-to-back launches, HIP events). Experiment harness for kernel
-knobs (OSPF_BLOCK, OSPF_FORCE_VARIANT). Prints one JSON line per config."""
+knobs (OSPF_FORCE_VARIANT, OSPF_MS_PACK, ...). Prints one JSON line per config."""
 import argparse
 import json
 import os
@@ -23,7 +23,6 @@ ap.add_argument("--planes", type=int, default=8)
 ap.add_argument("--W", type=int, nargs="+", default=[1, 3, 56])
 ap.add_argument("--n", type=int, nargs="+", default=[256, 1024, 4096])
 ap.add_argument("--reps", type=int, default=3)
-ap.add_argument("--blocks", type=int, nargs="+", default=[0])
 ap.add_argument("--envs", nargs="+", default=[""],
                 help="engine env configs to sweep, each 'K=V,K=V' ('' = defaults)")
 ap.add_argument("--order", choices=["auto", "random", "locality"], default="auto",
@@ -53,14 +52,10 @@ for W in args.W:
         dist = torch.empty((n, V), dtype=torch.int32, device="cuda")
         nh = torch.empty((n, V, W), dtype=torch.int32, device="cuda")
         dig = torch.empty((n, 3), dtype=torch.int64, device="cuda")
-        for blk, envc in [(b_, e_) for b_ in args.blocks for e_ in args.envs]:
+        for envc in args.envs:
             for kv in [x for x in envc.split(",") if x]:
                 k_, v_ = kv.split("=")
                 os.environ[k_] = v_
-            if blk:
-                os.environ["OSPF_BLOCK"] = str(blk)
-            else:
-                os.environ.pop("OSPF_BLOCK", None)
             hint = int(nbrs[members].max())
             plan = eng.plan(W, flags, n_roots=n, max_root_neighbors=hint)
             ts = []

@@ -178,6 +178,24 @@ int odl_spf_digests(odl_ls* ls, const char* roots_nl, uint32_t n, int use_link_m
 int odl_all_sources_prefetch(odl_ls* ls, int use_link_metric);
 int odl_all_sources_digests(odl_ls* ls, int use_link_metric, uint64_t* out);
 void odl_sweep_stats(const odl_ls* ls, uint64_t* out5);
+/* SpfSolver::getNextHopsWithMetric (SpfSolver.cpp:1043-1089) for every node
+ * and every prefix of a table, selected on the device from the all-sources
+ * sweep's resident rows (ospf_sweep_select / ospf_msweep_select; the host
+ * path computes the same from getSpfResult of every node). prefixes_nl: one
+ * prefix per line, its announcer node names tab-separated (an empty line: no
+ * announcer); names unknown to the LinkState and duplicates are dropped.
+ * Outputs by node id (odl_node_name order), any may be NULL:
+ *   metric [V][n_prefixes]  smallest metric over the announcers the node
+ *                           reaches, OSPF_DIST_INF when none;
+ *   count  [V][n_prefixes]  announcers at that metric (0 when none);
+ *   nh     [V][n_prefixes][nh_words]  union of their next hops, bit k = the
+ *                           node's k-th distinct neighbour in ascending id order.
+ * *nh_words_needed (optional) = the next-hop words of the widest node.
+ * nh_words = 0 asks for that width only: nothing else is read or written.
+ * nh_words below it fails (-1, odl_last_error). */
+int odl_all_sources_select(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefixes,
+                           int use_link_metric, uint32_t nh_words, uint32_t* nh_words_needed,
+                           uint32_t* metric, uint32_t* count, uint32_t* nh);
 /* Fill the getSpfResult memo for many roots with one engine batch. */
 int odl_spf_prefetch(odl_ls* ls, const char* roots_nl, uint32_t n, int use_link_metric);
 /* getKthPaths(src, d, 2) for every d, masked reruns batched on the engine;

@@ -621,6 +621,42 @@ int ospf_sweep_row(const ospf_sweep* sw, uint32_t root, const uint32_t** d_dist,
  * NULL. */
 int ospf_sweep_copy_rows(ospf_sweep* sw, const uint32_t* roots, uint32_t n, uint32_t nh_words,
                          uint32_t* dist_out, uint32_t* nh_out);
+/* Anycast route selection over the sweep's resident rows:
+ * SpfSolver::getNextHopsWithMetric (openr/decision/SpfSolver.cpp:1043-1089)
+ * for every owned root and every prefix of a table, in one launch, instead
+ * of ospf_sweep_copy_rows + a host loop per root. The table is CSR in host
+ * memory: prefix p is announced by nodes[offsets[p] .. offsets[p + 1]), node
+ * ids strictly ascending within a prefix (a prefix may be empty). Outputs, in
+ * ospf_sweep_roots order:
+ *   metric [n_roots][P]  the smallest dist[root][a] over the announcers a the
+ *                        root reaches (an announcer absent from the SPF result
+ *                        is skipped, :1065-1068); OSPF_DIST_INF when none is;
+ *   count  [n_roots][P]  announcers at that metric (minCostNodes, :1070-1076;
+ *                        0 when none is reached);
+ *   nh     [n_roots][P][nh_words]  the OR of those announcers' next-hop words
+ *                        (:1080-1086), bit order of ospf_root_neighbors; a
+ *                        root's words W .. nh_words are zero.
+ * A root that announces the prefix itself gets metric 0, count 1 and no next
+ * hop (its own SPF entry). Any output may be NULL (not wanted); every word of
+ * a wanted output is written, once. nh_words >= the sweep's max_nh_words.
+ * Preconditions as ospf_sweep_copy_rows: the sweep has run and its rows are
+ * complete (the _dev call does not wait for streams other than `stream`).
+ * OSPF_E_INVAL (reason in ospf_sweep_last_error, nothing written): an id >= V,
+ * a list not strictly ascending, offsets not monotone, nh_words too small,
+ * no run yet. n_prefixes == 0 or a part without roots: OSPF_OK, nothing
+ * written. The row table is uploaded once per sweep, the prefix table on
+ * every call (synchronously, before the kernel is queued on `stream`). */
+typedef struct ospf_select_table { /* host memory */
+  uint32_t n_prefixes;
+  const uint32_t* offsets; /* [n_prefixes + 1] */
+  const uint32_t* nodes;   /* announcer ids, strictly ascending per prefix */
+} ospf_select_table;
+/* device outputs, queued on `stream` after the table's upload */
+int ospf_sweep_select_dev(ospf_sweep* sw, const ospf_select_table* table, uint32_t nh_words,
+                          uint32_t* d_metric, uint32_t* d_count, uint32_t* d_nh, void* stream);
+/* host outputs, synchronous (after the work queued on every stream) */
+int ospf_sweep_select(ospf_sweep* sw, const ospf_select_table* table, uint32_t nh_words,
+                      uint32_t* metric, uint32_t* count, uint32_t* nh);
 /* Time every launch unit alone on its stream: reps (>= 1) timed launches
  * after one untimed one; fills min(cap, n_launches) records. The sweep must
  * have run once. */
@@ -664,6 +700,12 @@ int ospf_msweep_run(ospf_msweep* ms);
  * one scatter by root id and one copy back. OSPF_RCCL=1 takes RCCL for a
  * single device too (a one-rank communicator). */
 int ospf_msweep_digests(ospf_msweep* ms, ospf_digest* out_by_node);
+/* ospf_sweep_select on every part for its own roots (the parts' kernels run
+ * side by side, one per device); host outputs by node id: metric / count
+ * [V][P], nh [V][P][nh_words] (nh_words >= every part's max_nh_words). Errors
+ * through ospf_multi_last_error. */
+int ospf_msweep_select(ospf_msweep* ms, const ospf_select_table* table, uint32_t nh_words,
+                       uint32_t* metric_by_node, uint32_t* count_by_node, uint32_t* nh_by_node);
 /* 1: this sweep's digests are gathered by RCCL, 0: by peer copies. */
 uint32_t ospf_msweep_gather_backend(const ospf_msweep* ms);
 /* The slot's sweep (row access, info) and the slot owning `root`. */
@@ -677,7 +719,8 @@ uint64_t ospf_spf_runs(const ospf_ctx* ctx);
 
 /* Test hook (fault injection): the after_calls-th call from now of
  * ospf_load_graph / ospf_sssp_batch / ospf_ksp2_run / ospf_sweep_create /
- * ospf_sweep_run / ospf_sweep_copy_rows on this context fails with
+ * ospf_sweep_run / ospf_sweep_copy_rows / ospf_sweep_select_dev /
+ * ospf_sweep_select / ospf_msweep_select (per part) on this context fails with
  * OSPF_E_DEVICE and does nothing (0 = off). Lets the caller's handling of a
  * device error be tested without a faulting GPU. */
 int ospf_inject_error(ospf_ctx* ctx, uint32_t after_calls);

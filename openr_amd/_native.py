@@ -40,6 +40,7 @@ ENGINE_SYMBOLS = [
     "ospf_sweep_roots", "ospf_sweep_run", "ospf_sweep_digests", "ospf_sweep_digests_host",
     "ospf_sweep_poison",
     "ospf_sweep_row", "ospf_sweep_copy_rows", "ospf_sweep_profile", "ospf_sweep_graph_memsets",
+    "ospf_sweep_select_dev", "ospf_sweep_select", "ospf_msweep_select",
     "ospf_multi_open", "ospf_multi_close", "ospf_multi_last_error", "ospf_multi_size",
     "ospf_multi_ctx", "ospf_multi_load_graph", "ospf_msweep_create", "ospf_msweep_destroy",
     "ospf_msweep_run", "ospf_msweep_digests", "ospf_msweep_part", "ospf_msweep_owner",
@@ -53,7 +54,7 @@ DECISION_SYMBOLS = [
     "odl_ksp2_text", "odl_route_text", "odl_route_db_text", "odl_route_db_bin", "odl_free_buf", "odl_path_a_in_b", "odl_ucmp_text", "odl_csr_size", "odl_csr_export", "odl_node_name", "odl_node_id",
     "odl_apply_kvs", "odl_apply_publication", "odl_node_patches", "odl_shard_stats", "odl_route_db_multi_text", "odl_adjdbs_decode", "odl_adjdbs_stream", "odl_adjdbs_error", "odl_adjdbs_free",
     "odl_last_decode_error", "odl_get_counters", "odl_last_engine_error", "odl_inject_engine_error",
-    "odl_set_degrade",
+    "odl_set_degrade", "odl_all_sources_select",
 ]
 
 
@@ -123,6 +124,10 @@ class ospf_sweep_launch(C.Structure):  # noqa: N801
     _fields_ = [("name", C.c_char * 32), ("kernel", C.c_char * 112), ("n_roots", u32),
                 ("nh_words", u32), ("compulsory_bytes", u64), ("ms_median", C.c_double),
                 ("ms_min", C.c_double)]
+
+
+class ospf_select_table(C.Structure):  # noqa: N801
+    _fields_ = [("n_prefixes", u32), ("offsets", vp), ("nodes", vp)]
 
 
 class odl_counters(C.Structure):  # noqa: N801
@@ -206,6 +211,9 @@ def engine() -> C.CDLL:
         L.ospf_sweep_poison.argtypes = [vp, vp]
         L.ospf_sweep_row.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
         L.ospf_sweep_copy_rows.argtypes = [vp, vp, u32, u32, vp, vp]
+        L.ospf_sweep_select_dev.argtypes = [vp, C.POINTER(ospf_select_table), u32, vp, vp, vp, vp]
+        L.ospf_sweep_select.argtypes = [vp, C.POINTER(ospf_select_table), u32, vp, vp, vp]
+        L.ospf_msweep_select.argtypes = [vp, C.POINTER(ospf_select_table), u32, vp, vp, vp]
         L.ospf_sweep_profile.argtypes = [vp, u32, vp, u32]
         L.ospf_sweep_graph_memsets.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.ospf_multi_open.argtypes = [vp, u32, C.POINTER(vp)]
@@ -241,6 +249,7 @@ def decision() -> C.CDLL:
         L.odl_create_multi.argtypes = [cp, vp, u32, C.POINTER(vp)]
         L.odl_all_sources_prefetch.argtypes = [vp, i32]
         L.odl_all_sources_digests.argtypes = [vp, i32, vp]
+        L.odl_all_sources_select.argtypes = [vp, cp, u32, i32, u32, C.POINTER(u32), vp, vp, vp]
         L.odl_sweep_stats.argtypes = [vp, vp]
         L.odl_sweep_stats.restype = None
         L.odl_destroy.argtypes = [vp]

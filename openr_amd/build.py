@@ -24,7 +24,7 @@ ENGINE_SRC = [os.path.join(PKG, "csrc", "engine", f)
                         "spf_dial.hip", "spf_wdial.hip", "spf_wderive.hip", "spf_levels.hip",
                         "spf_cover.hip", "spf_msdist.hip", "spf_update.hip", "spf_leaf.hip", "spf_twin.hip", "spf_small.hip",
                         "spf_probe.hip", "spf_engine.hip",
-                        "spf_sweep.hip")]
+                        "spf_sweep.hip", "spf_select.hip")]
 DECISION_SRC = [os.path.join(PKG, "csrc", "decision", f)
                 for f in ("link_state.cpp", "spf_solver.cpp", "adjdb_thrift.cpp", "decision_capi.cpp")]
 ENGINE_SO = os.path.join(LIB, "libopenr_spf_hip.so")

@@ -376,6 +376,34 @@ int odl_all_sources_digests(odl_ls* h, int use_link_metric, uint64_t* out) {
   }, -1);
 }
 
+int odl_all_sources_select(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes,
+                           int use_link_metric, uint32_t nh_words, uint32_t* nh_words_needed,
+                           uint32_t* metric, uint32_t* count, uint32_t* nh) {
+  return guard(h, [&]() -> int {
+    const uint32_t need = h->ls.selectWords();
+    if (nh_words_needed) *nh_words_needed = need;
+    if (!nh_words) return 0;  // the width only
+    if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
+    std::vector<std::vector<std::string>> prefixes;
+    prefixes.reserve(n_prefixes);
+    for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
+      std::vector<std::string> names;
+      for (size_t b = 0; b < ln.size();) {  // tab-separated, empty fields skipped
+        size_t e = ln.find('\t', b);
+        if (e == std::string::npos) e = ln.size();
+        if (e > b) names.emplace_back(ln, b, e - b);
+        b = e + 1;
+      }
+      prefixes.push_back(std::move(names));
+    }
+    const auto r = h->ls.allSourcesSelect(prefixes, use_link_metric != 0, nh_words);
+    if (metric) std::copy(r.metric.begin(), r.metric.end(), metric);
+    if (count) std::copy(r.count.begin(), r.count.end(), count);
+    if (nh) std::copy(r.nh.begin(), r.nh.end(), nh);
+    return 0;
+  }, -1);
+}
+
 int odl_all_sources_prefetch(odl_ls* h, int use_link_metric) {
   return guard(h, [&]() -> int {
     h->ls.prefetchAllSources(use_link_metric != 0);

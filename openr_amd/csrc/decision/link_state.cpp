@@ -1116,6 +1116,112 @@ std::vector<ospf_digest> LinkState::allSourcesDigestsImpl(bool useLinkMetric) {
   return out;
 }
 
+uint32_t LinkState::selectWords() {
+  snapshot();
+  uint32_t W = 1;
+  for (uint32_t v = 0; v < csr_->names.size(); ++v) W = std::max(W, nhWordsFor(v));
+  return W;
+}
+
+LinkState::SelectResult LinkState::allSourcesSelect(
+    const std::vector<std::vector<std::string>>& prefixes, bool useLinkMetric, uint32_t nhWords) {
+  snapshot();
+  const uint32_t need = selectWords();
+  if (nhWords && nhWords < need)
+    throw std::invalid_argument("allSourcesSelect: nhWords " + std::to_string(nhWords) +
+                                " below the widest node's " + std::to_string(need));
+  // names -> ids: unknown names dropped, ascending and distinct per prefix
+  std::vector<std::vector<uint32_t>> ann(prefixes.size());
+  for (size_t p = 0; p < prefixes.size(); ++p) {
+    for (const auto& nm : prefixes[p]) {
+      const auto it = csr_->ids.find(nm);
+      if (it != csr_->ids.end()) ann[p].push_back(it->second);
+    }
+    std::sort(ann[p].begin(), ann[p].end());
+    ann[p].erase(std::unique(ann[p].begin(), ann[p].end()), ann[p].end());
+  }
+  const uint32_t W = nhWords ? nhWords : need;
+  return guarded([&] { return allSourcesSelectImpl(ann, useLinkMetric, W); });
+}
+
+LinkState::SelectResult LinkState::allSourcesSelectImpl(
+    const std::vector<std::vector<uint32_t>>& ann, bool useLinkMetric, uint32_t W) {
+  snapshot();
+  const size_t V = csr_->names.size(), P = ann.size();
+  SelectResult out;
+  out.prefixes = (uint32_t)P;
+  out.words = W;
+  out.metric.assign(V * P, kInf);
+  out.count.assign(V * P, 0);
+  out.nh.assign(V * P * W, 0);
+  if (!V || !P) return out;
+  if (hostRun(useLinkMetric)) {
+    // the reference loop (SpfSolver.cpp:1058-1086) over getSpfResult of every node
+    std::vector<uint32_t> nbrs;
+    for (uint32_t r = 0; r < V; ++r) {
+      const SpfResult& res = getSpfResult(csr_->names[r], useLinkMetric);
+      nbrs.clear();  // distinct neighbours, ascending: the bit order (nhWordsFor)
+      for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e)
+        if (csr_->col[e] != r && (nbrs.empty() || nbrs.back() != csr_->col[e]))
+          nbrs.push_back(csr_->col[e]);
+      for (size_t p = 0; p < P; ++p) {
+        Metric shortest = std::numeric_limits<Metric>::max();
+        std::vector<uint32_t> minCost;
+        for (uint32_t a : ann[p]) {
+          const auto it = res.find(csr_->names[a]);
+          if (it == res.end()) continue;
+          const Metric d = it->second.metric();
+          if (shortest >= d) {
+            if (shortest > d) {
+              shortest = d;
+              minCost.clear();
+            }
+            minCost.push_back(a);
+          }
+        }
+        if (minCost.empty()) continue;
+        out.metric[r * P + p] = (uint32_t)shortest;
+        out.count[r * P + p] = (uint32_t)minCost.size();
+        uint32_t* words = out.nh.data() + (r * P + p) * W;
+        for (uint32_t a : minCost)
+          for (const auto& nhName : res.at(csr_->names[a]).nextHops()) {
+            const uint32_t id = csr_->ids.at(nhName);
+            const uint32_t k = (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), id) - nbrs.begin());
+            if (k < nbrs.size() && nbrs[k] == id && k / 32 < W) words[k / 32] |= 1u << (k % 32);
+          }
+      }
+    }
+    return out;
+  }
+  prefetchAllSources(useLinkMetric);
+  std::vector<uint32_t> off(P + 1, 0), nodes;
+  for (size_t p = 0; p < P; ++p) {
+    nodes.insert(nodes.end(), ann[p].begin(), ann[p].end());
+    off[p + 1] = (uint32_t)nodes.size();
+  }
+  const ospf_select_table t{(uint32_t)P, off.data(), nodes.data()};
+  if (msweep_) {
+    const int rc = ospf_msweep_select(msweep_, &t, W, out.metric.data(), out.count.data(),
+                                      out.nh.data());
+    if (rc != OSPF_OK) throw EngineError(rc, ospf_multi_last_error(multi_));
+    return out;
+  }
+  ospf_sweep_info info{};
+  ospf_sweep_get_info(sweep_, &info);
+  std::vector<uint32_t> roots(info.n_roots);
+  ospf_sweep_roots(sweep_, roots.data());
+  std::vector<uint32_t> m(roots.size() * P), k(roots.size() * P), nh(roots.size() * P * W);
+  const int rc = ospf_sweep_select(sweep_, &t, W, m.data(), k.data(), nh.data());
+  if (rc != OSPF_OK) throw EngineError(rc, ospf_sweep_last_error(sweep_));
+  for (size_t i = 0; i < roots.size(); ++i) {  // owned-roots order -> node id
+    const size_t r = roots[i];
+    std::copy(m.begin() + i * P, m.begin() + (i + 1) * P, out.metric.begin() + r * P);
+    std::copy(k.begin() + i * P, k.begin() + (i + 1) * P, out.count.begin() + r * P);
+    std::copy(nh.begin() + i * P * W, nh.begin() + (i + 1) * P * W, out.nh.begin() + r * P * W);
+  }
+  return out;
+}
+
 void LinkState::evictSpf(const std::vector<std::string>& roots, bool useLinkMetric) {
   auto& memo = useLinkMetric ? memoMetric_ : memoHops_;
   for (const auto& r : roots) memo.erase(r);

@@ -536,6 +536,27 @@ class LinkState {
   void prefetchAllSources(bool useLinkMetric = true);
   // digests of every node (node-id order = snapshot().names) from one sweep
   std::vector<ospf_digest> allSourcesDigests(bool useLinkMetric = true);
+  // SpfSolver::getNextHopsWithMetric (SpfSolver.cpp:1043-1089) for every node
+  // and every prefix of a table, on the sweep's resident rows
+  // (ospf_sweep_select / ospf_msweep_select) instead of one getSpfResult per
+  // node: per node id and prefix the smallest metric over the announcers the
+  // node reaches (kInf: none), the number of announcers at it and the union of
+  // their next hops as `words` u32 per (node, prefix), bit k = the node's k-th
+  // distinct neighbour in ascending id order (nhWordsFor). Announcer names
+  // unknown to the snapshot are dropped (a node absent from the SPF result,
+  // :1065-1068), duplicates too. nhWords 0 = selectWords(); a smaller value
+  // throws std::invalid_argument. On the host path (setHostSpf, metrics
+  // outside the engine contract, after a device error) the same arrays come
+  // from getSpfResult of every node and the reference loop.
+  struct SelectResult {
+    uint32_t prefixes = 0, words = 0;
+    std::vector<uint32_t> metric, count;  // [V][prefixes]
+    std::vector<uint32_t> nh;             // [V][prefixes][words]
+  };
+  SelectResult allSourcesSelect(const std::vector<std::vector<std::string>>& prefixes,
+                                bool useLinkMetric = true, uint32_t nhWords = 0);
+  // next-hop words of the widest node of the snapshot
+  uint32_t selectWords();
   bool isMemoised(const std::string& root, bool useLinkMetric) const {
     return (useLinkMetric ? memoMetric_ : memoHops_).count(root) > 0;
   }
@@ -750,6 +771,8 @@ class LinkState {
   std::vector<ospf_digest> spfDigestsImpl(const std::vector<std::string>& roots, bool useLinkMetric);
   void prefetchAllSourcesImpl(bool useLinkMetric);
   std::vector<ospf_digest> allSourcesDigestsImpl(bool useLinkMetric);
+  SelectResult allSourcesSelectImpl(const std::vector<std::vector<uint32_t>>& ann,
+                                    bool useLinkMetric, uint32_t W);
   const std::vector<Path>& getKthPathsImpl(const std::string& src, const std::string& dst, size_t k);
   void prefetchKsp2Impl(const std::string& src, const std::vector<std::string>& dsts);
   bool hostRun(bool useLinkMetric) const { return hostOnly_ || (useLinkMetric && hostMetric_); }

@@ -254,6 +254,21 @@ int wderive_wide(ospf_ctx* c, const uint32_t* d_roots, uint32_t n, uint32_t flag
                  const uint32_t* d_pos, uint32_t* d_nh, ospf_digest* d_digest, void* stream,
                  uint32_t ctiles);
 
+// One owned root's rows in a sweep's device row table (ospf_sweep_select*):
+// dist u32[V], next hops u32[V][W].
+struct SelRow {
+  const uint32_t* dist;
+  const uint32_t* nh;
+  uint32_t W, pad;
+};
+// queue spf_select.hip's select_kernel: for every row of d_rows [n_roots] and
+// every prefix of the CSR table (d_off [n_prefixes + 1], d_nodes) the metric,
+// tie count and next-hop words (each output [n_roots][n_prefixes]([nh_words]),
+// null: not written); nh_words >= every row's W
+int select_launch(ospf_ctx* c, const SelRow* d_rows, uint32_t n_roots, const uint32_t* d_off,
+                  const uint32_t* d_nodes, uint32_t n_prefixes, uint32_t nh_words,
+                  uint32_t* d_metric, uint32_t* d_count, uint32_t* d_nh, void* stream);
+
 }  // namespace ospf_int
 
 #define HIPCHK(ctx, call)                                            \

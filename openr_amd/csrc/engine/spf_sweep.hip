@@ -254,6 +254,13 @@ struct ospf_sweep {
   // level launches the HIP graph captures (0: the graph's transit-depth bound)
   uint32_t* d_lv_maxd = nullptr;
   uint32_t lv_cap = 0;
+  // ospf_sweep_select*: the owned roots' rows as a device table (uploaded on
+  // first use), the last prefix table's device copy (offsets, then nodes;
+  // grown on demand) and the event after the last launch that reads it
+  ospf_int::SelRow* d_sel_rows = nullptr;
+  uint32_t* d_sel_tab = nullptr;
+  size_t sel_tab_words = 0;
+  hipEvent_t sel_ev = nullptr;
 };
 
 namespace {
@@ -2652,6 +2659,15 @@ void release(ospf_sweep* s) {
     if (e) hipEventDestroy(e);
   if (s->ev_in) hipEventDestroy(s->ev_in);
   if (s->ev_out) hipEventDestroy(s->ev_out);
+  if (s->sel_ev) {
+    hipEventSynchronize(s->sel_ev);
+    hipEventDestroy(s->sel_ev);
+  }
+  if (s->d_sel_tab) hipFree(s->d_sel_tab);
+  s->sel_ev = nullptr;
+  s->d_sel_tab = nullptr;
+  s->d_sel_rows = nullptr;  // one of allocs
+  s->sel_tab_words = 0;
   for (hipStream_t st : s->streams) {
     if (!st) continue;
     if (s->c) {
@@ -2671,6 +2687,95 @@ void release(ospf_sweep* s) {
   s->exec = nullptr;
   s->graph = nullptr;
 }
+
+// ---------------------------------------------------------------- select
+uint32_t max_row_words(const ospf_sweep* s) {
+  uint32_t mw = 0;
+  for (uint32_t r : s->roots) mw = std::max(mw, s->row_w[r]);
+  return mw;
+}
+
+// the table's contract (ospf_select_table): null on success, else what is wrong
+const char* select_table_error(const ospf_select_table* t, uint32_t V) {
+  if (!t) return "select: null table";
+  const uint32_t P = t->n_prefixes;
+  if (!P) return nullptr;
+  if (!t->offsets) return "select: null offsets";
+  for (uint32_t p = 0; p < P; ++p)
+    if (t->offsets[p] > t->offsets[p + 1]) return "select: offsets not monotone";
+  if (t->offsets[P] && !t->nodes) return "select: null nodes";
+  for (uint32_t p = 0; p < P; ++p)
+    for (uint32_t k = t->offsets[p]; k < t->offsets[p + 1]; ++k) {
+      if (t->nodes[k] >= V) return "select: announcer id outside the graph";
+      if (k > t->offsets[p] && t->nodes[k - 1] >= t->nodes[k])
+        return "select: announcers of a prefix not strictly ascending";
+    }
+  return nullptr;
+}
+
+// ospf_sweep_select_dev without the fault-injection hook (the host and
+// multi-device calls hook once themselves)
+int select_queue(ospf_sweep* s, const ospf_select_table* t, uint32_t nh_words, uint32_t* d_metric,
+                 uint32_t* d_count, uint32_t* d_nh, void* stream) {
+  if (!s->ran) return sfail(s, OSPF_E_INVAL, "sweep: select before the first run");
+  if (const char* bad = select_table_error(t, s->V)) return sfail(s, OSPF_E_INVAL, bad);
+  if (nh_words < max_row_words(s))
+    return sfail(s, OSPF_E_INVAL, "sweep: nh_words below a root's next-hop words");
+  const uint32_t n = (uint32_t)s->roots.size(), P = t->n_prefixes;
+  if (!n || !P || (!d_metric && !d_count && !d_nh)) return OSPF_OK;
+  SCHK(s, hipSetDevice(s->c->device));
+  if (!s->d_sel_rows) {  // once per sweep: the host row vectors, owned-roots order
+    std::vector<ospf_int::SelRow> h(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t r = s->roots[i];
+      h[i] = ospf_int::SelRow{s->row_dist[r], s->row_nh[r], s->row_w[r], 0u};
+    }
+    ospf_int::SelRow* d = nullptr;
+    const int rc = upload(s, &d, h);
+    if (rc) return rc;
+    s->d_sel_rows = d;
+  }
+  // the prefix table's device copy: the buffer is the last call's, free once
+  // that call's kernel is done
+  const size_t A = t->offsets[P], words = (size_t)P + 1 + A;
+  if (s->sel_ev) SCHK(s, hipEventSynchronize(s->sel_ev));
+  if (words > s->sel_tab_words) {
+    if (s->d_sel_tab) SCHK(s, hipFree(s->d_sel_tab));
+    s->d_sel_tab = nullptr;
+    s->sel_tab_words = 0;
+    void* q = nullptr;
+    if (hipMalloc(&q, words * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      return sfail(s, OSPF_E_NOMEM, "select: hipMalloc of the prefix table");
+    }
+    s->d_sel_tab = (uint32_t*)q;
+    s->sel_tab_words = words;
+  }
+  SCHK(s, hipMemcpy(s->d_sel_tab, t->offsets, ((size_t)P + 1) * 4, hipMemcpyHostToDevice));
+  if (A) SCHK(s, hipMemcpy(s->d_sel_tab + P + 1, t->nodes, A * 4, hipMemcpyHostToDevice));
+  if (!s->sel_ev) SCHK(s, hipEventCreateWithFlags(&s->sel_ev, hipEventDisableTiming));
+  const int rc = ospf_int::select_launch(s->c, s->d_sel_rows, n, s->d_sel_tab, s->d_sel_tab + P + 1,
+                                         P, nh_words, d_metric, d_count, d_nh, stream);
+  if (rc) return sfail(s, rc, s->c->err);
+  SCHK(s, hipEventRecord(s->sel_ev, (hipStream_t)stream));
+  return OSPF_OK;
+}
+
+// device outputs of one select ([n][P], [n][P], [n][P][W]; only the wanted
+// ones), freed by the destructor
+struct SelectOut {
+  uint32_t *m = nullptr, *k = nullptr, *nh = nullptr;
+  ~SelectOut() {
+    if (m) hipFree(m);
+    if (k) hipFree(k);
+    if (nh) hipFree(nh);
+  }
+  bool alloc(size_t cells, uint32_t W, bool wm, bool wk, bool wnh) {
+    return (!wm || hipMalloc((void**)&m, cells * 4) == hipSuccess) &&
+           (!wk || hipMalloc((void**)&k, cells * 4) == hipSuccess) &&
+           (!wnh || hipMalloc((void**)&nh, cells * W * 4) == hipSuccess);
+  }
+};
 
 }  // namespace
 
@@ -3027,6 +3132,35 @@ int ospf_sweep_copy_rows(ospf_sweep* s, const uint32_t* roots, uint32_t n, uint3
   return OSPF_OK;
 }
 
+int ospf_sweep_select_dev(ospf_sweep* s, const ospf_select_table* t, uint32_t nh_words,
+                          uint32_t* d_metric, uint32_t* d_count, uint32_t* d_nh, void* stream) {
+  if (!s || !t) return OSPF_E_INVAL;
+  if (ospf_int::injected(s->c)) return sfail(s, OSPF_E_DEVICE, s->c->err);
+  return select_queue(s, t, nh_words, d_metric, d_count, d_nh, stream);
+}
+
+int ospf_sweep_select(ospf_sweep* s, const ospf_select_table* t, uint32_t nh_words,
+                      uint32_t* metric, uint32_t* count, uint32_t* nh) {
+  if (!s || !t) return OSPF_E_INVAL;
+  if (ospf_int::injected(s->c)) return sfail(s, OSPF_E_DEVICE, s->c->err);
+  const size_t cells = s->roots.size() * (size_t)t->n_prefixes;
+  SelectOut d;
+  if (cells && s->ran) {
+    SCHK(s, hipSetDevice(s->c->device));
+    SCHK(s, hipDeviceSynchronize());  // the rows, whichever streams ran the sweep
+    if (!d.alloc(cells, std::max(1u, nh_words), metric, count, nh)) {
+      (void)hipGetLastError();
+      return sfail(s, OSPF_E_NOMEM, "select: hipMalloc of the outputs");
+    }
+  }
+  const int rc = select_queue(s, t, nh_words, d.m, d.k, d.nh, nullptr);
+  if (rc || !cells) return rc;
+  if (d.m) SCHK(s, hipMemcpy(metric, d.m, cells * 4, hipMemcpyDeviceToHost));
+  if (d.k) SCHK(s, hipMemcpy(count, d.k, cells * 4, hipMemcpyDeviceToHost));
+  if (d.nh) SCHK(s, hipMemcpy(nh, d.nh, cells * nh_words * 4, hipMemcpyDeviceToHost));
+  return OSPF_OK;
+}
+
 int ospf_sweep_profile(ospf_sweep* s, uint32_t reps, ospf_sweep_launch* out, uint32_t cap) {
   if (!s || (cap && !out)) return OSPF_E_INVAL;
   if (!s->ran) return sfail(s, OSPF_E_INVAL, "sweep: profile needs one run first");
@@ -3366,6 +3500,61 @@ int ospf_msweep_digests(ospf_msweep* ms, ospf_digest* out) {
       hipSuccess) {
     ms->m->err = "msweep: hipMemcpy";
     return OSPF_E_DEVICE;
+  }
+  return OSPF_OK;
+}
+
+int ospf_msweep_select(ospf_msweep* ms, const ospf_select_table* t, uint32_t nh_words,
+                       uint32_t* metric, uint32_t* count, uint32_t* nh) {
+  if (!ms || !t) return OSPF_E_INVAL;
+  const size_t n = ms->parts.size(), P = t->n_prefixes;
+  auto part_fail = [&](size_t i, int rc) {
+    ms->m->err = ms->parts[i]->err;
+    return rc;
+  };
+  auto dev_fail = [&](const char* what) {
+    (void)hipGetLastError();
+    ms->m->err = std::string("msweep select: ") + what;
+    return OSPF_E_DEVICE;
+  };
+  // every part queues its own roots' select on its device, then the copies
+  std::vector<SelectOut> d(n);
+  for (size_t i = 0; i < n; ++i) {
+    ospf_sweep* s = ms->parts[i];
+    if (ospf_int::injected(s->c)) return part_fail(i, sfail(s, OSPF_E_DEVICE, s->c->err));
+    const size_t cells = s->roots.size() * P;
+    if (cells && s->ran) {
+      if (hipSetDevice(s->c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return dev_fail("hipDeviceSynchronize");
+      if (!d[i].alloc(cells, std::max(1u, nh_words), metric, count, nh)) {
+        (void)hipGetLastError();
+        ms->m->err = "msweep select: hipMalloc of the outputs";
+        return OSPF_E_NOMEM;
+      }
+    }
+    const int rc = select_queue(s, t, nh_words, d[i].m, d[i].k, d[i].nh, nullptr);
+    if (rc) return part_fail(i, rc);
+  }
+  std::vector<uint32_t> tmp;
+  for (size_t i = 0; i < n; ++i) {
+    ospf_sweep* s = ms->parts[i];
+    const size_t cells = s->roots.size() * P;
+    if (!cells) continue;
+    if (hipSetDevice(s->c->device) != hipSuccess) return dev_fail("hipSetDevice");
+    // owned-roots order -> node id order, `per` words per (root, prefix)
+    auto by_node = [&](const uint32_t* dsrc, uint32_t* out, size_t per) {
+      if (!dsrc) return true;
+      tmp.resize(cells * per);
+      if (hipMemcpy(tmp.data(), dsrc, tmp.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return false;
+      for (size_t k = 0; k < s->roots.size(); ++k)
+        std::copy(tmp.begin() + k * P * per, tmp.begin() + (k + 1) * P * per,
+                  out + (size_t)s->roots[k] * P * per);
+      return true;
+    };
+    if (!by_node(d[i].m, metric, 1) || !by_node(d[i].k, count, 1) ||
+        !by_node(d[i].nh, nh, nh_words))
+      return dev_fail("hipMemcpy");
   }
   return OSPF_OK;
 }

@@ -32,6 +32,16 @@ def csr_struct(csr: Dict[str, np.ndarray]):
     return s, keep
 
 
+def select_table(offsets: Sequence[int], nodes: Sequence[int]):
+    """(ospf_select_table, the arrays it points into) of a CSR prefix table."""
+    off = np.ascontiguousarray(offsets, np.uint32)
+    ids = np.ascontiguousarray(nodes, np.uint32)
+    if off.size < 1:
+        raise ValueError("offsets needs n_prefixes + 1 entries")
+    t = N.ospf_select_table(int(off.size - 1), off.ctypes.data, ids.ctypes.data if ids.size else None)
+    return t, (off, ids)
+
+
 def decode_paths(recs: np.ndarray, status: np.ndarray, bad: int):
     """KSP2 records -> per row a list of paths (lists of link ids), None when
     `status & bad`."""
@@ -390,6 +400,30 @@ class Sweep:
                                                  dist.ctypes.data, nh.ctypes.data))
         return dist, nh
 
+    def select(self, offsets: Sequence[int], nodes: Sequence[int], nh_words: int = 0):
+        """ospf_sweep_select: getNextHopsWithMetric for every owned root and
+        every prefix of the CSR table (prefix p announced by
+        nodes[offsets[p]:offsets[p + 1]], ids strictly ascending) ->
+        (metric [n, P] u32, count [n, P] u32, nh [n, P, W] u32) in `roots`
+        order, W = nh_words or the sweep's max_nh_words."""
+        t, keep = select_table(offsets, nodes)
+        n, P, W = self.n_roots, int(t.n_prefixes), nh_words or max(1, self.max_nh_words)
+        metric = np.zeros((n, P), np.uint32)
+        count = np.zeros((n, P), np.uint32)
+        nh = np.zeros((n, P, W), np.uint32)
+        self._check(self._L.ospf_sweep_select(self._h, C.byref(t), W, metric.ctypes.data,
+                                              count.ctypes.data, nh.ctypes.data))
+        return metric, count, nh
+
+    def select_dev(self, offsets: Sequence[int], nodes: Sequence[int], nh_words: int, *,
+                   d_metric: int = 0, d_count: int = 0, d_nh: int = 0, stream: int = 0) -> None:
+        """ospf_sweep_select_dev: the same into device memory (raw pointers,
+        [n, P] / [n, P] / [n, P, nh_words] u32; 0 = not wanted), queued on
+        `stream` after the table's upload."""
+        t, keep = select_table(offsets, nodes)
+        self._check(self._L.ospf_sweep_select_dev(self._h, C.byref(t), nh_words, d_metric or None,
+                                                  d_count or None, d_nh or None, stream or None))
+
     def profile(self, reps: int = 3):
         """Every launch unit timed alone on its stream -> list of dicts."""
         cap = max(1, self.n_launches)
@@ -470,6 +504,25 @@ class MultiSweep:
         out = np.zeros((self.multi.V, 3), np.uint64)
         self.multi._check(self._L.ospf_msweep_digests(self._h, out.ctypes.data))
         return out
+
+    def select(self, offsets: Sequence[int], nodes: Sequence[int], nh_words: int = 0):
+        """ospf_msweep_select: every part selects for its own roots ->
+        (metric [V, P], count [V, P], nh [V, P, W]) by node id, W = nh_words
+        or the widest part's max_nh_words."""
+        t, keep = select_table(offsets, nodes)
+        if not nh_words:
+            gi = N.ospf_sweep_info()
+            for slot in range(self.multi.n):
+                self._L.ospf_sweep_get_info(self._L.ospf_msweep_part(self._h, slot), C.byref(gi))
+                nh_words = max(nh_words, int(gi.max_nh_words), 1)
+        V, P = self.multi.V, int(t.n_prefixes)
+        metric = np.zeros((V, P), np.uint32)
+        count = np.zeros((V, P), np.uint32)
+        nh = np.zeros((V, P, nh_words), np.uint32)
+        self.multi._check(self._L.ospf_msweep_select(self._h, C.byref(t), nh_words,
+                                                     metric.ctypes.data, count.ctypes.data,
+                                                     nh.ctypes.data))
+        return metric, count, nh
 
     @property
     def gather_backend(self) -> str:

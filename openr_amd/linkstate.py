@@ -110,6 +110,38 @@ def _parse_spf(t: str) -> Dict[str, Tuple[int, tuple, tuple]]:
     return out
 
 
+def root_neighbor_ids(csr: Dict[str, np.ndarray], root: int) -> np.ndarray:
+    """Distinct neighbours of `root` in ascending id order: the bit order of
+    every next-hop mask of that root (ospf_root_neighbors)."""
+    row = csr["col"][int(csr["row_ptr"][root]): int(csr["row_ptr"][root + 1])]
+    return np.unique(row[row != root])
+
+
+def decode_next_hops(csr: Dict[str, np.ndarray], names: Sequence[str], root, words) -> List[str]:
+    """(root id or name, mask words) -> next-hop node names, ascending id."""
+    rid = names.index(root) if isinstance(root, str) else int(root)
+    nb = root_neighbor_ids(csr, rid)
+    bits = np.unpackbits(np.ascontiguousarray(words, "<u4").view(np.uint8), bitorder="little")
+    on = np.nonzero(bits)[0]
+    if on.size and int(on[-1]) >= nb.size:
+        raise ValueError(f"mask bit {int(on[-1])} beyond the {nb.size} neighbours of node {rid}")
+    return [names[int(nb[k])] for k in on]
+
+
+def encode_next_hops(csr: Dict[str, np.ndarray], names: Sequence[str], root, hops: Sequence[str],
+                     nh_words: int) -> np.ndarray:
+    """Inverse of decode_next_hops: next-hop names -> nh_words mask words."""
+    rid = names.index(root) if isinstance(root, str) else int(root)
+    nb = root_neighbor_ids(csr, rid)
+    out = np.zeros(nh_words, np.uint32)
+    for h in hops:
+        k = int(np.searchsorted(nb, names.index(h)))
+        if k >= nb.size or int(nb[k]) != names.index(h):
+            raise ValueError(f"{h} is no neighbour of node {rid}")
+        out[k // 32] |= np.uint32(1 << (k % 32))
+    return out
+
+
 _FWDS = {"ip": 0, "sr_mpls": 1}
 _ALGOS = {"ecmp": 0, "ksp2": 1, "ucmp_adj": 2, "ucmp_prefix": 3}
 _TXT_OPS = {"0": "", "1": "PHP", "2": "SWAP", "3": "PUSH", "4": "POP"}
@@ -503,6 +535,44 @@ class LinkState:
         if self._L.odl_all_sources_digests(self._h, int(use_link_metric), out.ctypes.data) != 0:
             raise LinkStateError(self._err())
         return out
+
+    def all_sources_select(self, prefixes: Dict[str, Sequence[str]],
+                           use_link_metric: bool = True, nh_words: int = 0):
+        """SpfSolver::getNextHopsWithMetric for every node and every prefix
+        (odl_all_sources_select), selected on the device from the all-sources
+        sweep's rows. prefixes: {prefix: announcer node names}; unknown names
+        and duplicates are dropped. Returns (metric [V, P] u32, count [V, P]
+        u32, nh [V, P, W] u32) by node id (node_names() order), columns in the
+        dict's order; metric 0xFFFFFFFF / count 0 where the node reaches no
+        announcer; decode nh with next_hop_names()."""
+        lines = ["\t".join(a) for a in prefixes.values()]
+        for ln in lines:
+            if "\n" in ln:
+                raise ValueError("node names must not contain newlines")
+        txt = "\n".join(lines).encode()
+        need = C.c_uint32(0)
+        if self._L.odl_all_sources_select(self._h, txt, len(lines), int(use_link_metric), 0,
+                                          C.byref(need), None, None, None) != 0:
+            raise LinkStateError(self._err())
+        V, P, W = self.num_nodes(), len(lines), nh_words or int(need.value)
+        metric = np.zeros((V, P), np.uint32)
+        count = np.zeros((V, P), np.uint32)
+        nh = np.zeros((V, P, W), np.uint32)
+        if self._L.odl_all_sources_select(self._h, txt, P, int(use_link_metric), W, None,
+                                          metric.ctypes.data, count.ctypes.data,
+                                          nh.ctypes.data) != 0:
+            raise LinkStateError(self._err())
+        return metric, count, nh
+
+    def next_hop_names(self, root, words, csr: Optional[Dict[str, np.ndarray]] = None,
+                       names: Optional[Sequence[str]] = None) -> List[str]:
+        """Names of the next hops in one (root, prefix) mask of
+        all_sources_select: bit k of `words` = the root's k-th distinct
+        neighbour in ascending id order. root: node id or name; csr / names:
+        csr() / node_names() when the caller already holds them."""
+        csr = self.csr() if csr is None else csr
+        names = self.node_names() if names is None else names
+        return decode_next_hops(csr, names, root, words)
 
     def prefetch_all(self, use_link_metric: bool = True) -> None:
         if self._L.odl_all_sources_prefetch(self._h, int(use_link_metric)) != 0:

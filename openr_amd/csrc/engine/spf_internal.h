@@ -1,6 +1,7 @@
 // spf_internal.h — the engine context shared by the C ABI translation units
-// (spf_engine.hip: graph, batches, derive, KSP2, updates; spf_sweep.cpp:
-// all-sources sweeps and the multi-device context). Not a public header.
+// (spf_engine.hip: graph, batches, derive, KSP2, updates; the sweep's units
+// behind sweep_impl.h: all-sources sweeps and the multi-device context). Not a
+// public header.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -45,6 +45,80 @@ def drained_fabric(pods, planes, seed=0, drain=0.05, down=0.03, weighted_seed=No
     return AdjDbStream.from_dbs(dbs)
 
 
+def deep_ladder(S, stage_width=2, *, ends=False, seed_stage=None, islands=(), hub=0,
+                weighted_seed=None):
+    """AdjDbs of a unit-metric ladder of S stages of `stage_width` nodes: every
+    node of stage i is linked to every node of stages i - 1 and i + 1, none
+    inside a stage, so the nodes of a stage are twins (same neighbours, 2
+    apart, stage_width ECMP next hops towards anything beyond) at every depth.
+
+    Names (ids are name ranks): stage i holds s{i:03d}a, s{i:03d}b, ...; with
+    `seed_stage` its first node is named a{i:03d} instead and so is the
+    lowest-id transit node, where the engine seeds its depth bound:
+    2 * max(seed_stage, S - 1 - seed_stage) + 2.
+    ends: overloaded (non-transit) e0 on all of stage 0 and e1 on all of
+    stage S - 1 (S + 1 hops apart; outside the bound, still roots and
+    destinations). hub=n: overloaded h linked to every node of stages
+    0 .. n - 1 (stage_width * n distinct neighbours as a root; shortens
+    nothing). islands=(k, ...): k-node cliques z{j}a, z{j}b, ... unreachable
+    from the ladder and back. weighted_seed: random metrics 1..30 per
+    adjacency on the same links (for hop-count runs)."""
+    rng = None if weighted_seed is None else np.random.default_rng(weighted_seed)
+    stage = [[f"s{i:03d}{chr(97 + j)}" for j in range(stage_width)] for i in range(S)]
+    if seed_stage is not None:
+        stage[seed_stage][0] = f"a{seed_stage:03d}"
+    adjs, over = {nm: [] for st in stage for nm in st}, set()
+
+    def link(a, b):
+        for x, y in ((a, b), (b, a)):
+            m = 1 if rng is None else int(rng.integers(1, 31))
+            adjs[x].append(create_adjacency(y, f"{x}-{y}", f"{y}-{x}", m))
+
+    for i in range(S - 1):
+        for a in stage[i]:
+            for b in stage[i + 1]:
+                link(a, b)
+    extra = ([("e0", stage[0]), ("e1", stage[S - 1])] if ends else []) + \
+        ([("h", [nm for st in stage[:hub] for nm in st])] if hub else [])
+    for nm, nbrs in extra:
+        adjs[nm] = []
+        over.add(nm)
+        for b in nbrs:
+            link(nm, b)
+    for j, k in enumerate(islands):
+        isl = [f"z{j}{chr(97 + t)}" for t in range(k)]
+        adjs.update({nm: [] for nm in isl})
+        for t in range(k):
+            for u in range(t + 1, k):
+                link(isl[t], isl[u])
+    return [AdjDb(nm, adjs[nm], i + 1, overloaded=nm in over) for i, nm in enumerate(sorted(adjs))]
+
+
+def depth_bound(csr):
+    """The engine's BFS level bound (transit_depth_bound, spf_engine.hip)
+    restated over LinkState.csr(): 2 * ecc + 2, ecc the largest eccentricity,
+    within the transit subgraph (usable links between nodes that may relay),
+    of the lowest-id node of each of its components."""
+    rp, col, up, nt = csr["row_ptr"], csr["col"], csr["edge_up"], csr["no_transit"]
+    V = rp.size - 1
+    lvl = [-1] * V
+    ecc_max = 0
+    for s in range(V):
+        if nt[s] or lvl[s] >= 0:
+            continue
+        lvl[s] = 0
+        q = [s]
+        for u in q:
+            for e in range(int(rp[u]), int(rp[u + 1])):
+                x = int(col[e])
+                if not up[e] or nt[x] or lvl[x] >= 0:
+                    continue
+                lvl[x] = lvl[u] + 1
+                q.append(x)
+        ecc_max = max(ecc_max, lvl[q[-1]])
+    return 2 * ecc_max + 2
+
+
 def path_dbs(n):
     """A path p000 - p001 - ... of n nodes with unit metrics: n - 1 levels
     deep from either end (names sort in path order)."""

@@ -475,6 +475,13 @@ int ospf_sweep_create(ospf_ctx* c, const ospf_sweep_opts* o, ospf_sweep** out) {
   const uint32_t max_w = std::max(1u, (c->max_dn + 31) / 32);
   const bool lds_ok = unit && max_w <= 4 && ospf_lds_sweep_fits(c, o->flags & OSPF_HOP_COUNT, max_w) &&
                       !knob_flag(Knob::OSPF_SWEEP_NOLDS);
+  // the cover and multi-root paths derive the next hops of roots with > 128
+  // neighbours from a u16 slot table of their link metrics
+  // (wderive_lanes_kernel: metrics <= 0xFFFE): decided here, not by the
+  // unit's first launch. The rule is graph-wide, so it also turns away cover
+  // plans whose wide roots would all have taken their next hops from the
+  // seeds' Dial; AUTO then takes the weighted-derive sweep.
+  const bool lanes_ok = hop || max_w <= 4 || c->info.max_metric <= 0xFFFEu;
   std::vector<uint8_t> leaf;
   bool any_leaf = false;
   uint32_t mode = o->mode;
@@ -490,7 +497,7 @@ int ospf_sweep_create(ospf_ctx* c, const ospf_sweep_opts* o, ospf_sweep** out) {
       mode = OSPF_SWEEP_LDS;
     } else if (derive_ok) {
       mode = OSPF_SWEEP_DERIVE;
-    } else if (!hop && any_leaf && ospf_cover_prepare(c, leaf.data()) == OSPF_OK) {
+    } else if (!hop && any_leaf && lanes_ok && ospf_cover_prepare(c, leaf.data()) == OSPF_OK) {
       mode = OSPF_SWEEP_WCOVER;
     } else if (any_leaf) {
       mode = OSPF_SWEEP_WDERIVE;
@@ -505,8 +512,14 @@ int ospf_sweep_create(ospf_ctx* c, const ospf_sweep_opts* o, ospf_sweep** out) {
                                       "distinct neighbours per node and the graph in LDS"));
   } else if (mode == OSPF_SWEEP_WCOVER) {
     if (hop) return bail(fail(c, OSPF_E_INVAL, "sweep: the cover path runs link metrics"));
+    if (!lanes_ok)
+      return bail(fail(c, OSPF_E_RANGE, "sweep: the cover path needs metrics <= 65534 when a "
+                                        "node has more than 128 distinct neighbours"));
     const int rc = ospf_cover_prepare(c, leaf.data());
     if (rc) return bail(rc);
+  } else if (mode == OSPF_SWEEP_WMULTI && !lanes_ok) {
+    return bail(fail(c, OSPF_E_RANGE, "sweep: wmulti needs metrics <= 65534 when a node has "
+                                      "more than 128 distinct neighbours"));
   }
   s->mode = mode;
   lap("partition + leaf set + cover prepare");

@@ -137,6 +137,13 @@ struct GRun {
     return i < ign_n && ign[i] == l;
   }
   __device__ uint32_t slot_of(uint32_t dd) const { return (dd / delta) % NB; }
+  // the first distance past bucket b, saturated: the last bucket below 2^32
+  // ends at kInf (every finite distance is smaller) instead of wrapping to a
+  // small end that none of its entries is below
+  __device__ uint32_t bucket_end(uint32_t b) const {
+    const uint64_t e = ((uint64_t)b + 1ull) * delta;
+    return e > (uint64_t)kInf ? kInf : (uint32_t)e;
+  }
   __device__ uint32_t* entry(uint32_t s, uint32_t i) const {
     return lists + ((size_t)s * bcap + i) * (TAG ? 2u : 1u);
   }
@@ -404,7 +411,7 @@ struct GRun {
     const bool full = ovf(s);
     uint32_t nx = kInf;
     if (TAG) {  // the rest of this bucket first
-      nx = list_min(s, d + 1, (d / delta + 1) * delta);
+      nx = list_min(s, d + 1, bucket_end(d / delta));
       if (nx != kInf) {
         if (!full) compact(s, d);
         if (lane == 0) ctl->next = nx;
@@ -432,7 +439,7 @@ struct GRun {
         nx = b;  // delta == 1: the list's distance
         break;
       }
-      nx = list_min(qs, b * delta, (b + 1) * delta);
+      nx = list_min(qs, b * delta, bucket_end(b));
       if (nx != kInf) break;
       if (lane == 0) {  // only stale entries: drop the list, keep looking
         ctl->cnt[qs] = 0u;
@@ -489,7 +496,8 @@ struct GRun {
       for (uint32_t i = tid; i < V; i += nthr) {
         const uint32_t wd = ld2(&pk[i]);
         dist[i] = field(wd);
-        nh[i] = wd & nhmask;
+        // a node never reached keeps its initial all-ones word: no next hops
+        nh[i] = (wd >> K) == infk ? 0u : wd & nhmask;
       }
     }
     return true;

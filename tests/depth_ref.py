@@ -43,14 +43,23 @@ def ladder_dbs(name, weighted_seed=None):
     return deep_ladder(weighted_seed=weighted_seed, **SHAPES[name])
 
 
+def make_shape(name, dbs):
+    """stream, oracle, node names (id order), ids by name and read-only CSR of
+    a list of AdjDbs (the one definition metric_ref.py shares)"""
+    st = AdjDbStream.from_dbs(dbs)
+    ls = LinkState(stream=st)
+    names = ls.node_names()
+    csr = ls.csr()
+    for a in csr.values():
+        a.setflags(write=False)
+    return SimpleNamespace(name=name, stream=st, oracle=Oracle(st), names=names,
+                           ids={nm: i for i, nm in enumerate(names)}, csr=csr, V=len(names))
+
+
 @functools.lru_cache(maxsize=None)
 def shape(name, weighted_seed=None):
     """stream, oracle, node names (id order), ids by name and CSR of a shape"""
-    st = AdjDbStream.from_dbs(ladder_dbs(name, weighted_seed))
-    ls = LinkState(stream=st)
-    names = ls.node_names()
-    return SimpleNamespace(name=name, stream=st, oracle=Oracle(st), names=names,
-                           ids={nm: i for i, nm in enumerate(names)}, csr=ls.csr(), V=len(names))
+    return make_shape(name, ladder_dbs(name, weighted_seed))
 
 
 def words_of(csr, r):
@@ -79,12 +88,11 @@ def rows_of(g, res, r, W):
     return dist, nh
 
 
-@functools.lru_cache(maxsize=None)
-def expected(name, use_link_metric=True, weighted_seed=None, roots=None):
-    """Rows of `roots` (a tuple of ids; None = every node) by next-hop word
-    count: {W: (root ids [n] u32 ascending, dist [n, V] u32, nh [n, V, W]
-    u32)}. Shared by the tests: read only."""
-    g = shape(name, weighted_seed)
+def expected_rows(g, spf_of, roots=None):
+    """Rows of `roots` (ids; None = every node) of shape g by next-hop word
+    count, spf_of(root name) -> the oracle's parsed runSpf:
+    {W: (root ids [n] u32 ascending, dist [n, V] u32, nh [n, V, W] u32)},
+    read only."""
     rs = np.arange(g.V, dtype=np.uint32) if roots is None else np.array(sorted(roots), np.uint32)
     words = np.array([words_of(g.csr, int(r)) for r in rs])
     out = {}
@@ -93,20 +101,35 @@ def expected(name, use_link_metric=True, weighted_seed=None, roots=None):
         dist = np.zeros((grp.size, g.V), np.uint32)
         nh = np.zeros((grp.size, g.V, W), np.uint32)
         for j, r in enumerate(grp.tolist()):
-            dist[j], nh[j] = rows_of(g, spf(name, g.names[r], use_link_metric, weighted_seed), r, W)
+            dist[j], nh[j] = rows_of(g, spf_of(g.names[r]), r, W)
         for a in (grp, dist, nh):
             a.setflags(write=False)
         out[W] = (grp, dist, nh)
     return out
 
 
+def oracle_digests(g, use_link_metric=True, fast=False):
+    """{reached, sumDist, digest} of every root of shape g, node id order,
+    [V, 3] u64, read only (fast: the oracle's CSR-Dijkstra restatement)"""
+    f = g.oracle.fast_digests if fast else g.oracle.digests
+    d = f(g.names, use_link_metric, threads=8)
+    d.setflags(write=False)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name, use_link_metric=True, weighted_seed=None, roots=None):
+    """Rows of `roots` (a tuple of ids; None = every node) by next-hop word
+    count: {W: (root ids [n] u32 ascending, dist [n, V] u32, nh [n, V, W]
+    u32)}. Shared by the tests: read only."""
+    return expected_rows(shape(name, weighted_seed),
+                         lambda r: spf(name, r, use_link_metric, weighted_seed), roots)
+
+
 @functools.lru_cache(maxsize=None)
 def digests(name, use_link_metric=True, weighted_seed=None):
     """{reached, sumDist, digest} of every root, node id order, [V, 3] u64"""
-    g = shape(name, weighted_seed)
-    d = g.oracle.digests(g.names, use_link_metric, threads=8)
-    d.setflags(write=False)
-    return d
+    return oracle_digests(shape(name, weighted_seed), use_link_metric)
 
 
 def sample_roots(name):

@@ -129,3 +129,46 @@ def path_dbs(n):
         adjs[a].append(create_adjacency(b, f"{a}-{b}", f"{b}-{a}", 1))
         adjs[b].append(create_adjacency(a, f"{b}-{a}", f"{a}-{b}", 1))
     return [AdjDb(nm, adjs[nm], i + 1) for i, nm in enumerate(names)]
+
+
+def metric_graph(links, overloaded=()):
+    """AdjDbs of an explicit weighted graph. links: (a, b, w_ab, w_ba) or
+    (a, b, w_ab, w_ba, "down") -- one adjacency per direction with its own
+    metric; "down" reports a's side overloaded (the link is unusable both
+    ways). `overloaded`: names of no-transit nodes. Ids are name ranks."""
+    adjs = {}
+    for k, ln in enumerate(links):
+        a, b, wab, wba = ln[:4]
+        down = len(ln) > 4 and ln[4] == "down"
+        adjs.setdefault(a, []).append(create_adjacency(b, f"{a}-{b}-{k}", f"{b}-{a}-{k}", int(wab),
+                                                       overloaded=down))
+        adjs.setdefault(b, []).append(create_adjacency(a, f"{b}-{a}-{k}", f"{a}-{b}-{k}", int(wba)))
+    return [AdjDb(nm, adjs[nm], i + 1, overloaded=nm in overloaded)
+            for i, nm in enumerate(sorted(adjs))]
+
+
+def furniture(at, island=2, tag="f"):
+    """(links, overloaded names) of what every limit shape carries besides
+    its critical path, hung off node `at`: an ECMP diamond at -> {fa, fb} ->
+    fc (3 either way, asymmetric per direction), an overloaded node fo on fa
+    and fc (a destination, never a relay), a down link fa - fb, and an
+    island za - zb - ... of `island` nodes nothing else reaches."""
+    fa, fb, fc, fo = (tag + x for x in "abco")
+    links = [(at, fa, 1, 2), (at, fb, 2, 1), (fa, fc, 2, 1), (fb, fc, 1, 2),
+             (fa, fo, 1, 3), (fc, fo, 3, 1), (fa, fb, 1, 1, "down")]
+    isl = [f"z{chr(97 + t)}" for t in range(island)]
+    links += [(isl[t], isl[t + 1], 5 + t, 7 + t) for t in range(island - 1)]
+    return links, {fo}
+
+
+def dist_bound(csr):
+    """The engine's distance bound (the l_bound loop of ospf_load_graph)
+    restated over LinkState.csr(): the sum over all nodes -- overloaded ones
+    too -- of the largest metric on an out-entry whose link is up; a node
+    with no usable entry adds 0."""
+    rp, met, up = csr["row_ptr"], csr["metric"], csr["edge_up"]
+    total = 0
+    for u in range(rp.size - 1):
+        row = [int(met[e]) for e in range(int(rp[u]), int(rp[u + 1])) if up[e]]
+        total += max(row, default=0)
+    return total

@@ -196,6 +196,39 @@ void odl_sweep_stats(const odl_ls* ls, uint64_t* out5);
 int odl_all_sources_select(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefixes,
                            int use_link_metric, uint32_t nh_words, uint32_t* nh_words_needed,
                            uint32_t* metric, uint32_t* count, uint32_t* nh);
+/* Only the selections a topology change altered (LinkState::trackSelect /
+ * selectDelta / selectTracked): DecisionRouteDb::calculateUpdate
+ * (SpfSolver.cpp:24-59) for odl_all_sources_select's route DB.
+ * odl_track_select binds the LinkState to a prefix table (prefixes_nl as
+ * above) and stores the current snapshot's selection as the baseline, on the
+ * device (ospf_selstate_*). odl_select_delta re-sweeps when the graph version
+ * moved and returns the entries that differ from the baseline, then makes the
+ * new selection the baseline:
+ *   *changes  odl_select_change[*n_changes], the NEW values, order unspecified;
+ *   *nh       uint32 [*n_changes][*nh_words], record i's next-hop words (bit k
+ *             = the node's k-th distinct neighbour), zero-padded;
+ *   *rebased  uint32 [*n_rebased] node ids whose distinct-neighbour list
+ *             changed: none of their entries is listed (their bits mean other
+ *             neighbours now) -- read them with odl_select_tracked;
+ *   *full     1 when the node-name set changed since the last call (ids were
+ *             renumbered): the baseline was taken again and no list is
+ *             returned; read everything anew.
+ * The three buffers are malloc'd (free each with odl_free_buf). A prefix that
+ * lost its last reached announcer comes back with metric OSPF_DIST_INF and
+ * count 0. odl_select_tracked copies the baseline of n nodes (names, one per
+ * line) as odl_all_sources_select lays it out: metric / count [n][P], nh
+ * [n][P][nh_words] (0 = the baseline's width; any output may be NULL). On the
+ * host path (odl_set_host_spf, metrics outside the engine contract, after a
+ * device error) and on a multi-device LinkState the previous selection is
+ * kept on the host and diffed there: the same answers. */
+typedef struct odl_select_change {
+  uint32_t node, prefix, metric, count;
+} odl_select_change;
+int odl_track_select(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefixes, int use_link_metric);
+int odl_select_delta(odl_ls* ls, uint32_t* n_changes, uint32_t* n_rebased, uint32_t* nh_words,
+                     int* full, void** changes, void** nh, void** rebased);
+int odl_select_tracked(odl_ls* ls, const char* nodes_nl, uint32_t n, uint32_t nh_words,
+                       uint32_t* metric, uint32_t* count, uint32_t* nh);
 /* Fill the getSpfResult memo for many roots with one engine batch. */
 int odl_spf_prefetch(odl_ls* ls, const char* roots_nl, uint32_t n, int use_link_metric);
 /* getKthPaths(src, d, 2) for every d, masked reruns batched on the engine;

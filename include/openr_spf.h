@@ -657,6 +657,63 @@ int ospf_sweep_select_dev(ospf_sweep* sw, const ospf_select_table* table, uint32
 /* host outputs, synchronous (after the work queued on every stream) */
 int ospf_sweep_select(ospf_sweep* sw, const ospf_select_table* table, uint32_t nh_words,
                       uint32_t* metric, uint32_t* count, uint32_t* nh);
+/* Only the route selections a re-sweep changed: the counterpart of
+ * DecisionRouteDb::calculateUpdate (openr/decision/SpfSolver.cpp:24-59, called
+ * from Decision.cpp:963) for the route DB ospf_sweep_select answers. An
+ * ospf_selstate belongs to a context, not to a sweep (a sweep lives for one
+ * graph version), and to one prefix table, copied at create (contract and
+ * errors of ospf_select_table as above, against the loaded graph's V). It
+ * keeps the selection of every root resident on the device in the root's own
+ * width: per root metric [P], count [P], nh [P][W_root], indexed by NODE ID
+ * (ospf_sweep_roots order changes between plans), twice (double-buffered).
+ *   prime   stores sw's selection as the baseline; reports nothing.
+ *   update  computes sw's selection into the shadow buffer (its own per-root
+ *           offsets: W_root may have changed), compares it on the device with
+ *           the stored one and returns the entries that changed, then commits
+ *           by swapping the buffers. Host outputs, synchronous.
+ *   copy    the stored selection of `roots`, expanded as ospf_sweep_select
+ *           does: metric / count [n][P], nh [n][P][nh_words] (a root's words
+ *           W_root .. nh_words zero); any output may be NULL.
+ * A root's entry for a prefix is {metric, count, its W_root next-hop words},
+ * exactly as ospf_sweep_select defines them; an entry changed when any of them
+ * differs. A prefix that lost its last reached announcer comes back as metric
+ * = OSPF_DIST_INF, count = 0: the caller's route to delete. A change record
+ * carries the NEW values; nh[i] holds record i's words zero-padded to
+ * nh_words (nh may be NULL; nh_words >= the sweep's max_nh_words either way).
+ * The order of the records is unspecified.
+ * Next-hop bits are positions in the root's distinct-neighbour list
+ * (ospf_root_neighbors). When that list differs between the stored version
+ * and sw's graph the old and new words are not comparable (equal words can
+ * mean different neighbours), so the state keeps every root's list (dn_off /
+ * dn, about E words) and compares it on the device: a root whose list changed
+ * is "rebased" -- reported once in rebased_roots, none of its entries listed;
+ * the caller reads them with ospf_selstate_copy.
+ * sw must belong to the state's context, have run, describe the context's
+ * current graph, and own every node of a graph with the state's V: anything
+ * else (another V, a part of the roots) is OSPF_E_INVAL with the state
+ * untouched. Several parts / ospf_msweep are not supported here.
+ * n_changes > cap or n_rebased > cap_rebased: OSPF_E_RANGE with both counts
+ * filled; the state is UNCHANGED and whatever the lists hold is to be
+ * ignored -- the caller retries with larger capacities and gets the complete
+ * set. update / copy before prime: OSPF_E_INVAL. n_prefixes == 0: OSPF_OK with
+ * zero counts. Any failure (an injected one included) leaves the state as it
+ * was. Errors through ospf_selstate_last_error (and ospf_last_error). */
+typedef struct ospf_selstate ospf_selstate;
+typedef struct ospf_select_change {
+  uint32_t root, prefix, metric, count;
+} ospf_select_change;
+int ospf_selstate_create(ospf_ctx* ctx, const ospf_select_table* table, ospf_selstate** out);
+int ospf_selstate_destroy(ospf_selstate* st);
+const char* ospf_selstate_last_error(const ospf_selstate* st);
+/* device memory the state holds now (both buffers, lists, the table) */
+uint64_t ospf_selstate_device_bytes(const ospf_selstate* st);
+int ospf_selstate_prime(ospf_selstate* st, ospf_sweep* sw);
+int ospf_selstate_update(ospf_selstate* st, ospf_sweep* sw, uint32_t nh_words,
+                         ospf_select_change* changes, uint32_t* nh /*[cap][nh_words]*/,
+                         uint32_t cap, uint32_t* n_changes, uint32_t* rebased_roots,
+                         uint32_t cap_rebased, uint32_t* n_rebased);
+int ospf_selstate_copy(ospf_selstate* st, const uint32_t* roots, uint32_t n, uint32_t nh_words,
+                       uint32_t* metric, uint32_t* count, uint32_t* nh);
 /* Time every launch unit alone on its stream: reps (>= 1) timed launches
  * after one untimed one; fills min(cap, n_launches) records. The sweep must
  * have run once. */
@@ -720,7 +777,8 @@ uint64_t ospf_spf_runs(const ospf_ctx* ctx);
 /* Test hook (fault injection): the after_calls-th call from now of
  * ospf_load_graph / ospf_sssp_batch / ospf_ksp2_run / ospf_sweep_create /
  * ospf_sweep_run / ospf_sweep_copy_rows / ospf_sweep_select_dev /
- * ospf_sweep_select / ospf_msweep_select (per part) on this context fails with
+ * ospf_sweep_select / ospf_msweep_select (per part) / ospf_selstate_prime /
+ * ospf_selstate_update / ospf_selstate_copy on this context fails with
  * OSPF_E_DEVICE and does nothing (0 = off). Lets the caller's handling of a
  * device error be tested without a faulting GPU. */
 int ospf_inject_error(ospf_ctx* ctx, uint32_t after_calls);

@@ -41,6 +41,8 @@ ENGINE_SYMBOLS = [
     "ospf_sweep_poison",
     "ospf_sweep_row", "ospf_sweep_copy_rows", "ospf_sweep_profile", "ospf_sweep_graph_memsets",
     "ospf_sweep_select_dev", "ospf_sweep_select", "ospf_msweep_select",
+    "ospf_selstate_create", "ospf_selstate_destroy", "ospf_selstate_last_error",
+    "ospf_selstate_device_bytes", "ospf_selstate_prime", "ospf_selstate_update", "ospf_selstate_copy",
     "ospf_multi_open", "ospf_multi_close", "ospf_multi_last_error", "ospf_multi_size",
     "ospf_multi_ctx", "ospf_multi_load_graph", "ospf_msweep_create", "ospf_msweep_destroy",
     "ospf_msweep_run", "ospf_msweep_digests", "ospf_msweep_part", "ospf_msweep_owner",
@@ -55,6 +57,7 @@ DECISION_SYMBOLS = [
     "odl_apply_kvs", "odl_apply_publication", "odl_node_patches", "odl_shard_stats", "odl_route_db_multi_text", "odl_adjdbs_decode", "odl_adjdbs_stream", "odl_adjdbs_error", "odl_adjdbs_free",
     "odl_last_decode_error", "odl_get_counters", "odl_last_engine_error", "odl_inject_engine_error",
     "odl_set_degrade", "odl_all_sources_select",
+    "odl_track_select", "odl_select_delta", "odl_select_tracked",
 ]
 
 
@@ -214,6 +217,16 @@ def engine() -> C.CDLL:
         L.ospf_sweep_select_dev.argtypes = [vp, C.POINTER(ospf_select_table), u32, vp, vp, vp, vp]
         L.ospf_sweep_select.argtypes = [vp, C.POINTER(ospf_select_table), u32, vp, vp, vp]
         L.ospf_msweep_select.argtypes = [vp, C.POINTER(ospf_select_table), u32, vp, vp, vp]
+        L.ospf_selstate_create.argtypes = [vp, C.POINTER(ospf_select_table), C.POINTER(vp)]
+        L.ospf_selstate_destroy.argtypes = [vp]
+        L.ospf_selstate_last_error.argtypes = [vp]
+        L.ospf_selstate_last_error.restype = cp
+        L.ospf_selstate_device_bytes.argtypes = [vp]
+        L.ospf_selstate_device_bytes.restype = u64
+        L.ospf_selstate_prime.argtypes = [vp, vp]
+        L.ospf_selstate_update.argtypes = [vp, vp, u32, vp, vp, u32, C.POINTER(u32), vp, u32,
+                                           C.POINTER(u32)]
+        L.ospf_selstate_copy.argtypes = [vp, vp, u32, u32, vp, vp, vp]
         L.ospf_sweep_profile.argtypes = [vp, u32, vp, u32]
         L.ospf_sweep_graph_memsets.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.ospf_multi_open.argtypes = [vp, u32, C.POINTER(vp)]
@@ -250,6 +263,10 @@ def decision() -> C.CDLL:
         L.odl_all_sources_prefetch.argtypes = [vp, i32]
         L.odl_all_sources_digests.argtypes = [vp, i32, vp]
         L.odl_all_sources_select.argtypes = [vp, cp, u32, i32, u32, C.POINTER(u32), vp, vp, vp]
+        L.odl_track_select.argtypes = [vp, cp, u32, i32]
+        L.odl_select_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
+                                       C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.odl_select_tracked.argtypes = [vp, cp, u32, u32, vp, vp, vp]
         L.odl_sweep_stats.argtypes = [vp, vp]
         L.odl_sweep_stats.restype = None
         L.odl_destroy.argtypes = [vp]

@@ -99,6 +99,34 @@ auto guard(odl_ls* h, F&& f, decltype(f()) bad) -> decltype(f()) {
 
 }  // namespace
 
+namespace {
+// prefix lines (one per prefix, announcer names tab-separated, empty fields skipped)
+std::vector<std::vector<std::string>> prefixLines(const char* prefixes_nl, uint32_t n_prefixes) {
+  if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
+  std::vector<std::vector<std::string>> prefixes;
+  prefixes.reserve(n_prefixes);
+  for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
+    std::vector<std::string> names;
+    for (size_t b = 0; b < ln.size();) {
+      size_t e = ln.find('\t', b);
+      if (e == std::string::npos) e = ln.size();
+      if (e > b) names.emplace_back(ln, b, e - b);
+      b = e + 1;
+    }
+    prefixes.push_back(std::move(names));
+  }
+  return prefixes;
+}
+
+template <class T>
+void* dupVec(const std::vector<T>& v) {
+  void* p = std::malloc(std::max<size_t>(1, v.size() * sizeof(T)));
+  if (!p) throw std::bad_alloc();
+  if (!v.empty()) std::memcpy(p, v.data(), v.size() * sizeof(T));
+  return p;
+}
+}  // namespace
+
 extern "C" {
 
 int odl_create(const char* area, int device, odl_ls** out) {
@@ -397,6 +425,54 @@ int odl_all_sources_select(odl_ls* h, const char* prefixes_nl, uint32_t n_prefix
       prefixes.push_back(std::move(names));
     }
     const auto r = h->ls.allSourcesSelect(prefixes, use_link_metric != 0, nh_words);
+    if (metric) std::copy(r.metric.begin(), r.metric.end(), metric);
+    if (count) std::copy(r.count.begin(), r.count.end(), count);
+    if (nh) std::copy(r.nh.begin(), r.nh.end(), nh);
+    return 0;
+  }, -1);
+}
+
+int odl_track_select(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes, int use_link_metric) {
+  return guard(h, [&]() -> int {
+    h->ls.trackSelect(prefixLines(prefixes_nl, n_prefixes), use_link_metric != 0);
+    return 0;
+  }, -1);
+}
+
+int odl_select_delta(odl_ls* h, uint32_t* n_changes, uint32_t* n_rebased, uint32_t* nh_words,
+                     int* full, void** changes, void** nh, void** rebased) {
+  return guard(h, [&]() -> int {
+    if (!n_changes || !n_rebased || !nh_words || !full || !changes || !nh || !rebased)
+      throw std::invalid_argument("null output pointer");
+    *changes = *nh = *rebased = nullptr;
+    const auto d = h->ls.selectDelta();
+    static_assert(sizeof(odl::LinkState::SelectChange) == 16, "odl_select_change layout");
+    void* a = dupVec(d.changes);
+    void* b = nullptr;
+    void* c = nullptr;
+    try {
+      b = dupVec(d.nh);
+      c = dupVec(d.rebased);
+    } catch (...) {
+      std::free(a);
+      std::free(b);
+      throw;
+    }
+    *changes = a;
+    *nh = b;
+    *rebased = c;
+    *n_changes = (uint32_t)d.changes.size();
+    *n_rebased = (uint32_t)d.rebased.size();
+    *nh_words = d.words;
+    *full = d.full ? 1 : 0;
+    return 0;
+  }, -1);
+}
+
+int odl_select_tracked(odl_ls* h, const char* nodes_nl, uint32_t n, uint32_t nh_words,
+                       uint32_t* metric, uint32_t* count, uint32_t* nh) {
+  return guard(h, [&]() -> int {
+    const auto r = h->ls.selectTracked(splitNl(nodes_nl ? nodes_nl : "", n), nh_words);
     if (metric) std::copy(r.metric.begin(), r.metric.end(), metric);
     if (count) std::copy(r.count.begin(), r.count.end(), count);
     if (nh) std::copy(r.nh.begin(), r.nh.end(), nh);

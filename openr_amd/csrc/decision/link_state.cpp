@@ -206,6 +206,7 @@ LinkState::LinkState(std::string area, std::vector<int> devices)
 LinkState::~LinkState() {
   joinOpen();
   reaper_.reset();  // drains the dropped memos, joins the thread
+  trackDropDev();
   dropSweep();
   if (multi_) ospf_multi_close(multi_);
   else if (engine_) ospf_close(engine_);
@@ -862,6 +863,10 @@ void LinkState::onEngineError(const std::exception& e) {
   lastEngineError_ = e.what();
   fprintf(stderr, "odl::LinkState(%s): engine error, continuing on the host path: %s\n",
           area_.c_str(), e.what());
+  // the tracked selection's baseline leaves the device with the engine (a
+  // device that cannot give it back: the next selectDelta reports `full`)
+  trackPull();
+  trackDropDev();
   dropSweep();
   if (multi_) ospf_multi_close(multi_);
   else if (engine_) ospf_close(engine_);
@@ -1220,6 +1225,203 @@ LinkState::SelectResult LinkState::allSourcesSelectImpl(
     std::copy(nh.begin() + i * P * W, nh.begin() + (i + 1) * P * W, out.nh.begin() + r * P * W);
   }
   return out;
+}
+
+// ---------------------------------------------------------------- trackSelect
+std::vector<std::vector<uint32_t>> LinkState::trackAnn() const {
+  // names -> ids as allSourcesSelect: unknown names dropped, ascending, distinct
+  std::vector<std::vector<uint32_t>> ann(trackPrefixes_.size());
+  for (size_t p = 0; p < trackPrefixes_.size(); ++p) {
+    for (const auto& nm : trackPrefixes_[p]) {
+      const auto it = csr_->ids.find(nm);
+      if (it != csr_->ids.end()) ann[p].push_back(it->second);
+    }
+    std::sort(ann[p].begin(), ann[p].end());
+    ann[p].erase(std::unique(ann[p].begin(), ann[p].end()), ann[p].end());
+  }
+  return ann;
+}
+
+void LinkState::trackDropDev() {
+  if (selstate_) ospf_selstate_destroy(selstate_);
+  selstate_ = nullptr;
+  trackDev_ = false;
+}
+
+void LinkState::trackPull() {
+  if (!trackDev_ || !selstate_) return;
+  const size_t V = trackNames_.size(), P = trackPrefixes_.size(), W = trackWords_;
+  std::vector<uint32_t> ids(V);
+  for (size_t i = 0; i < V; ++i) ids[i] = (uint32_t)i;
+  SelectResult r;
+  r.prefixes = (uint32_t)P;
+  r.words = (uint32_t)W;
+  r.metric.assign(V * P, kInf);
+  r.count.assign(V * P, 0);
+  r.nh.assign(V * P * W, 0);
+  const int rc = ospf_selstate_copy(selstate_, ids.data(), (uint32_t)V, (uint32_t)W, r.metric.data(),
+                                    r.count.data(), r.nh.data());
+  trackDev_ = false;
+  trackHostOk_ = rc == OSPF_OK;
+  if (trackHostOk_) trackHost_ = std::move(r);
+}
+
+void LinkState::trackPrime() {
+  snapshot();
+  const size_t V = csr_->names.size();
+  const auto ann = trackAnn();
+  trackDropDev();
+  trackHostOk_ = false;
+  trackHost_ = SelectResult{};
+  const uint32_t W = selectWords();
+  if (!hostRun(trackMetric_) && devices_.size() == 1 && V) {
+    prefetchAllSources(trackMetric_);
+    std::vector<uint32_t> off(ann.size() + 1, 0), nodes;
+    for (size_t p = 0; p < ann.size(); ++p) {
+      nodes.insert(nodes.end(), ann[p].begin(), ann[p].end());
+      off[p + 1] = (uint32_t)nodes.size();
+    }
+    const ospf_select_table t{(uint32_t)ann.size(), off.data(), nodes.data()};
+    int rc = ospf_selstate_create(engine_, &t, &selstate_);
+    if (rc != OSPF_OK) throw EngineError(rc, ospf_last_error(engine_));
+    rc = ospf_selstate_prime(selstate_, sweep_);
+    if (rc != OSPF_OK) {
+      const std::string m = ospf_selstate_last_error(selstate_);
+      trackDropDev();
+      throw EngineError(rc, m);
+    }
+    trackDev_ = true;
+  } else {
+    trackHost_ = allSourcesSelectImpl(ann, trackMetric_, W);
+    trackHostOk_ = true;
+  }
+  trackNames_ = csr_->names;
+  trackWords_ = W;
+  trackNbrs_.resize(V);
+  for (uint32_t v = 0; v < V; ++v) trackNbrs_[v] = nbrsOf(v);
+}
+
+void LinkState::trackSelect(const std::vector<std::vector<std::string>>& prefixes,
+                            bool useLinkMetric) {
+  trackPrefixes_ = prefixes;
+  trackMetric_ = useLinkMetric;
+  tracking_ = true;
+  guarded([&] { trackPrime(); });
+}
+
+LinkState::SelectDelta LinkState::selectDelta() {
+  if (!tracking_) throw std::logic_error("selectDelta: no tracked table (trackSelect)");
+  return guarded([&] { return selectDeltaImpl(); });
+}
+
+LinkState::SelectDelta LinkState::selectDeltaImpl() {
+  snapshot();
+  SelectDelta out;
+  const size_t V = csr_->names.size(), P = trackPrefixes_.size();
+  const uint32_t W = selectWords();
+  out.words = W;
+  // the ids were renumbered, or no baseline survived (a device error that
+  // took it along): everything anew
+  if (csr_->names != trackNames_ || (!trackDev_ && !trackHostOk_)) {
+    trackPrime();
+    out.full = true;
+    return out;
+  }
+  const bool dev = !hostRun(trackMetric_) && devices_.size() == 1;
+  if (dev && trackDev_) {
+    prefetchAllSources(trackMetric_);  // re-sweeps when the version moved
+    uint32_t cap = 1024, capReb = 64, n = 0, nReb = 0;
+    std::vector<ospf_select_change> recs;
+    for (;;) {
+      recs.resize(cap);
+      out.nh.assign((size_t)cap * W, 0);
+      out.rebased.assign(capReb, 0);
+      const int rc = ospf_selstate_update(selstate_, sweep_, W, recs.data(), out.nh.data(), cap, &n,
+                                          out.rebased.data(), capReb, &nReb);
+      if (rc == OSPF_OK) break;
+      if (rc != OSPF_E_RANGE) throw EngineError(rc, ospf_selstate_last_error(selstate_));
+      cap = std::max(cap, n);  // the state is unchanged: the same call, large enough
+      capReb = std::max(capReb, nReb);
+    }
+    out.changes.resize(n);
+    for (uint32_t i = 0; i < n; ++i)
+      out.changes[i] = SelectChange{recs[i].root, recs[i].prefix, recs[i].metric, recs[i].count};
+    out.nh.resize((size_t)n * W);
+    out.rebased.resize(nReb);
+    std::sort(out.rebased.begin(), out.rebased.end());
+  } else {
+    if (trackDev_) trackPull();  // the host takes over with the device's baseline
+    if (!trackHostOk_) {
+      trackPrime();
+      out.full = true;
+      return out;
+    }
+    trackDropDev();
+    SelectResult now = allSourcesSelectImpl(trackAnn(), trackMetric_, W);
+    const SelectResult& was = trackHost_;
+    for (uint32_t v = 0; v < V; ++v) {
+      if (nbrsOf(v) != trackNbrs_[v]) {
+        out.rebased.push_back(v);
+        continue;
+      }
+      for (size_t p = 0; p < P; ++p) {
+        const size_t i = v * P + p;
+        bool ch = now.metric[i] != was.metric[i] || now.count[i] != was.count[i];
+        for (uint32_t w = 0; w < std::max(W, was.words) && !ch; ++w)
+          ch = (w < W ? now.nh[i * W + w] : 0u) != (w < was.words ? was.nh[i * was.words + w] : 0u);
+        if (!ch) continue;
+        out.changes.push_back(SelectChange{v, (uint32_t)p, now.metric[i], now.count[i]});
+        out.nh.insert(out.nh.end(), now.nh.begin() + i * W, now.nh.begin() + (i + 1) * W);
+      }
+    }
+    trackHost_ = std::move(now);
+  }
+  trackWords_ = W;
+  for (uint32_t v : out.rebased) trackNbrs_[v] = nbrsOf(v);
+  return out;
+}
+
+LinkState::SelectResult LinkState::selectTracked(const std::vector<std::string>& nodes,
+                                                 uint32_t nhWords) {
+  if (!tracking_) throw std::logic_error("selectTracked: no tracked table (trackSelect)");
+  if (!trackDev_ && !trackHostOk_) throw std::logic_error("selectTracked: no baseline (selectDelta)");
+  const uint32_t W = nhWords ? nhWords : trackWords_;
+  if (W < trackWords_)
+    throw std::invalid_argument("selectTracked: nhWords " + std::to_string(W) +
+                                " below the baseline's " + std::to_string(trackWords_));
+  std::vector<uint32_t> ids;
+  for (const auto& nm : nodes) {
+    const auto it = std::lower_bound(trackNames_.begin(), trackNames_.end(), nm);
+    if (it == trackNames_.end() || *it != nm)
+      throw std::invalid_argument("selectTracked: unknown node " + nm);
+    ids.push_back((uint32_t)(it - trackNames_.begin()));
+  }
+  return guarded([&] {
+    const size_t n = ids.size(), P = trackPrefixes_.size();
+    SelectResult r;
+    r.prefixes = (uint32_t)P;
+    r.words = W;
+    r.metric.assign(n * P, kInf);
+    r.count.assign(n * P, 0);
+    r.nh.assign(n * P * W, 0);
+    if (trackDev_) {
+      const int rc = ospf_selstate_copy(selstate_, ids.data(), (uint32_t)n, W, r.metric.data(),
+                                        r.count.data(), r.nh.data());
+      if (rc != OSPF_OK) throw EngineError(rc, ospf_selstate_last_error(selstate_));
+      return r;
+    }
+    if (!trackHostOk_) throw std::logic_error("selectTracked: the baseline was lost (selectDelta)");
+    const SelectResult& h = trackHost_;
+    for (size_t i = 0; i < n; ++i) {
+      const size_t v = ids[i];
+      std::copy(h.metric.begin() + v * P, h.metric.begin() + (v + 1) * P, r.metric.begin() + i * P);
+      std::copy(h.count.begin() + v * P, h.count.begin() + (v + 1) * P, r.count.begin() + i * P);
+      for (size_t p = 0; p < P; ++p)
+        std::copy(h.nh.begin() + (v * P + p) * h.words, h.nh.begin() + (v * P + p + 1) * h.words,
+                  r.nh.begin() + (i * P + p) * W);
+    }
+    return r;
+  });
 }
 
 void LinkState::evictSpf(const std::vector<std::string>& roots, bool useLinkMetric) {

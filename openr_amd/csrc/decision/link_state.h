@@ -557,6 +557,40 @@ class LinkState {
                                 bool useLinkMetric = true, uint32_t nhWords = 0);
   // next-hop words of the widest node of the snapshot
   uint32_t selectWords();
+  // Only the selections a topology change altered: the counterpart of
+  // DecisionRouteDb::calculateUpdate (SpfSolver.cpp:24-59) for
+  // allSourcesSelect's route DB. trackSelect binds the LinkState to one
+  // prefix table (as allSourcesSelect takes it) and stores the selection of
+  // the current snapshot as the baseline (primed from prefetchAllSources,
+  // resident on the device: ospf_selstate_*). selectDelta re-sweeps when the
+  // graph version moved and returns the (node, prefix) entries whose metric,
+  // count or next-hop words differ from the baseline -- the new values, the
+  // words zero-padded to `words` = selectWords() -- then makes the new
+  // selection the baseline. A node whose distinct-neighbour list changed
+  // (its bits mean other neighbours) is listed in `rebased` instead of its
+  // entries: read those with selectTracked. When the node-name set changed
+  // since the last call the ids were renumbered: `full` is set, the baseline
+  // is taken again and no list is returned -- the caller reads everything
+  // (allSourcesSelect / selectTracked). selectTracked returns the baseline
+  // of some nodes in allSourcesSelect's layout (V = nodes.size()). On the
+  // host path (setHostSpf, metrics outside the engine contract, after a
+  // device error) the previous SelectResult is kept and diffed against a
+  // fresh reference loop: the same answers. A multi-device LinkState always
+  // takes that host diff, over allSourcesSelect (ospf_selstate is bound to
+  // one sweep that owns every root).
+  struct SelectChange {
+    uint32_t node, prefix, metric, count;
+  };
+  struct SelectDelta {
+    uint32_t words = 0;
+    std::vector<SelectChange> changes;
+    std::vector<uint32_t> nh;       // [changes][words]
+    std::vector<uint32_t> rebased;  // node ids
+    bool full = false;
+  };
+  void trackSelect(const std::vector<std::vector<std::string>>& prefixes, bool useLinkMetric = true);
+  SelectDelta selectDelta();
+  SelectResult selectTracked(const std::vector<std::string>& nodes, uint32_t nhWords = 0);
   bool isMemoised(const std::string& root, bool useLinkMetric) const {
     return (useLinkMetric ? memoMetric_ : memoHops_).count(root) > 0;
   }
@@ -773,6 +807,21 @@ class LinkState {
   std::vector<ospf_digest> allSourcesDigestsImpl(bool useLinkMetric);
   SelectResult allSourcesSelectImpl(const std::vector<std::vector<uint32_t>>& ann,
                                     bool useLinkMetric, uint32_t W);
+  // ---- trackSelect ----
+  bool tracking_ = false, trackMetric_ = true;
+  std::vector<std::vector<std::string>> trackPrefixes_;  // by name: ids move with the name set
+  std::vector<std::string> trackNames_;                  // node names of the baseline
+  std::vector<std::vector<uint32_t>> trackNbrs_;         // their distinct neighbours (bit order)
+  uint32_t trackWords_ = 1;                              // selectWords() of the baseline
+  ospf_selstate* selstate_ = nullptr;
+  bool trackDev_ = false;   // the baseline is the device state's
+  bool trackHostOk_ = false;  // the baseline is trackHost_
+  SelectResult trackHost_;
+  std::vector<std::vector<uint32_t>> trackAnn() const;  // the table by id, current snapshot
+  void trackPrime();                                    // the current snapshot as the baseline
+  void trackPull();   // the device baseline into trackHost_ (before the engine goes)
+  void trackDropDev();
+  SelectDelta selectDeltaImpl();
   const std::vector<Path>& getKthPathsImpl(const std::string& src, const std::string& dst, size_t k);
   void prefetchKsp2Impl(const std::string& src, const std::vector<std::string>& dsts);
   bool hostRun(bool useLinkMetric) const { return hostOnly_ || (useLinkMetric && hostMetric_); }

@@ -1443,6 +1443,9 @@ int ospf_close(ospf_ctx* c) {
   for (ospf_sweep* s : std::vector<ospf_sweep*>(c->live_sweeps))
     if (c->release_sweep) c->release_sweep(s);
   c->live_sweeps.clear();
+  for (ospf_selstate* st : std::vector<ospf_selstate*>(c->live_selstates))
+    if (c->release_selstate) c->release_selstate(st);
+  c->live_selstates.clear();
   if (c->d_graph) hipFree(c->d_graph);
   for (auto& kv : c->scratch)
     if (kv.second.p) hipFree(kv.second.p);

@@ -38,6 +38,10 @@ struct ospf_ctx {
   // GC order -- then frees only itself)
   std::vector<struct ospf_sweep*> live_sweeps;
   void (*release_sweep)(struct ospf_sweep*) = nullptr;
+  // the same for the select states (ospf_selstate_*: owned by the context,
+  // they outlive the sweeps of one graph version)
+  std::vector<struct ospf_selstate*> live_selstates;
+  void (*release_selstate)(struct ospf_selstate*) = nullptr;
   // graph
   bool loaded = false;
   ospf_graph_info info{};

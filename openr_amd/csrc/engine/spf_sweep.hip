@@ -353,6 +353,26 @@ const char* select_table_error(const ospf_select_table* t, uint32_t V) {
 
 }  // namespace
 
+const char* ospf_int::sweep::select_table_check(const ospf_select_table* t, uint32_t V) {
+  return select_table_error(t, V);
+}
+
+// the owned roots' rows as a device table (s->d_sel_rows), uploaded once per sweep
+int ospf_int::sweep::select_rows(ospf_sweep* s) {
+  if (s->d_sel_rows) return OSPF_OK;
+  const uint32_t n = (uint32_t)s->roots.size();
+  std::vector<ospf_int::SelRow> h(n);  // the host row vectors, owned-roots order
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t r = s->roots[i];
+    h[i] = ospf_int::SelRow{s->row_dist[r], s->row_nh[r], s->row_w[r], 0u};
+  }
+  ospf_int::SelRow* d = nullptr;
+  const int rc = upload(s, &d, h);
+  if (rc) return rc;
+  s->d_sel_rows = d;
+  return OSPF_OK;
+}
+
 // ospf_sweep_select_dev without the fault-injection hook (the host and
 // multi-device calls hook once themselves)
 int ospf_int::sweep::select_queue(ospf_sweep* s, const ospf_select_table* t, uint32_t nh_words, uint32_t* d_metric,
@@ -364,17 +384,7 @@ int ospf_int::sweep::select_queue(ospf_sweep* s, const ospf_select_table* t, uin
   const uint32_t n = (uint32_t)s->roots.size(), P = t->n_prefixes;
   if (!n || !P || (!d_metric && !d_count && !d_nh)) return OSPF_OK;
   SCHK(s, hipSetDevice(s->c->device));
-  if (!s->d_sel_rows) {  // once per sweep: the host row vectors, owned-roots order
-    std::vector<ospf_int::SelRow> h(n);
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint32_t r = s->roots[i];
-      h[i] = ospf_int::SelRow{s->row_dist[r], s->row_nh[r], s->row_w[r], 0u};
-    }
-    ospf_int::SelRow* d = nullptr;
-    const int rc = upload(s, &d, h);
-    if (rc) return rc;
-    s->d_sel_rows = d;
-  }
+  if (const int rc = select_rows(s)) return rc;
   // the prefix table's device copy: the buffer is the last call's, free once
   // that call's kernel is done
   const size_t A = t->offsets[P], words = (size_t)P + 1 + A;

@@ -244,6 +244,13 @@ int plan_wderive(ospf_sweep* s, const Facts& f, const std::vector<uint32_t>& min
 int select_queue(ospf_sweep* s, const ospf_select_table* t, uint32_t nh_words, uint32_t* d_metric,
                  uint32_t* d_count, uint32_t* d_nh, void* stream);
 
+// the table's contract (ospf_select_table) for a graph of V nodes: null when
+// it holds, else what is wrong
+const char* select_table_check(const ospf_select_table* t, uint32_t V);
+// the owned roots' rows as a device table (s->d_sel_rows, owned-roots order),
+// uploaded on first use
+int select_rows(ospf_sweep* s);
+
 // device outputs of one select ([n][P], [n][P], [n][P][W]; only the wanted
 // ones), freed by the destructor
 struct SelectOut {

@@ -42,6 +42,11 @@ def select_table(offsets: Sequence[int], nodes: Sequence[int]):
     return t, (off, ids)
 
 
+# ospf_select_change / odl_select_change records
+CHANGE_DTYPE = np.dtype([("root", np.uint32), ("prefix", np.uint32), ("metric", np.uint32),
+                         ("count", np.uint32)])
+
+
 def decode_paths(recs: np.ndarray, status: np.ndarray, bad: int):
     """KSP2 records -> per row a list of paths (lists of link ids), None when
     `status & bad`."""
@@ -441,6 +446,93 @@ class Sweep:
         a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
         self._check(self._L.ospf_sweep_graph_memsets(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return int(a.value), int(b.value), int(c.value)
+
+
+class SelStateOverflow(EngineError):
+    """ospf_selstate_update's OSPF_E_RANGE (-4): more changes or rebased
+    roots than the capacities; the state is unchanged. n_changes / n_rebased
+    are the complete counts to retry with."""
+
+    def __init__(self, msg: str, n_changes: int, n_rebased: int):
+        super().__init__(-4, msg)
+        self.n_changes = n_changes
+        self.n_rebased = n_rebased
+
+
+class SelState:
+    """ospf_selstate: the selection of one prefix table for every root, kept
+    on the device in each root's own width, and the entries a later sweep
+    changed (DecisionRouteDb::calculateUpdate for ospf_sweep_select's route
+    DB). Bound to an Engine (not to a Sweep) and to one table."""
+
+    def __init__(self, engine: "Engine", offsets: Sequence[int], nodes: Sequence[int]):
+        self._L = N.engine()
+        self.engine = engine
+        t, keep = select_table(offsets, nodes)
+        self.P = int(t.n_prefixes)
+        h = C.c_void_p()
+        rc = self._L.ospf_selstate_create(engine._h, C.byref(t), C.byref(h))
+        if rc != 0:
+            raise EngineError(rc, self._L.ospf_last_error(engine._h).decode())
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ospf_selstate_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+    def _msg(self) -> str:
+        return self._L.ospf_selstate_last_error(self._h).decode()
+
+    @property
+    def device_bytes(self) -> int:
+        return int(self._L.ospf_selstate_device_bytes(self._h))
+
+    def prime(self, sweep: "Sweep") -> None:
+        """Store the sweep's selection as the baseline; reports nothing."""
+        rc = self._L.ospf_selstate_prime(self._h, sweep._h)
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+
+    def update(self, sweep: "Sweep", cap: int = 1024, cap_rebased: int = 64, nh_words: int = 0,
+               want_nh: bool = True):
+        """Compare the sweep's selection with the stored one and commit it ->
+        (changes [n] structured u32 root / prefix / metric / count with the NEW
+        values, nh [n, W] u32 or None, rebased roots [m] u32). Raises
+        SelStateOverflow (code -4, n_changes / n_rebased attached, state
+        unchanged) when a list does not fit its capacity."""
+        if cap < 0 or cap_rebased < 0 or nh_words < 0:
+            raise ValueError("capacities and nh_words must be >= 0")
+        W = nh_words or max(1, sweep.max_nh_words)
+        rec = np.zeros(max(1, cap), CHANGE_DTYPE)
+        nh = np.zeros((max(1, cap), W), np.uint32) if want_nh else None
+        reb = np.zeros(max(1, cap_rebased), np.uint32)
+        n, m = C.c_uint32(), C.c_uint32()
+        rc = self._L.ospf_selstate_update(self._h, sweep._h, W, rec.ctypes.data,
+                                          nh.ctypes.data if want_nh else None, cap, C.byref(n),
+                                          reb.ctypes.data, cap_rebased, C.byref(m))
+        if rc == -4:
+            raise SelStateOverflow(self._msg(), int(n.value), int(m.value))
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+        return rec[: n.value], (nh[: n.value] if want_nh else None), reb[: m.value]
+
+    def copy(self, roots: Sequence[int], nh_words: int):
+        """The stored selection of `roots` (node ids), expanded like
+        Sweep.select: (metric [n, P], count [n, P], nh [n, P, nh_words])."""
+        roots = np.ascontiguousarray(roots, np.uint32)
+        if nh_words < 1:
+            raise ValueError("nh_words must be >= 1")
+        metric = np.zeros((roots.size, self.P), np.uint32)
+        count = np.zeros((roots.size, self.P), np.uint32)
+        nh = np.zeros((roots.size, self.P, nh_words), np.uint32)
+        rc = self._L.ospf_selstate_copy(self._h, roots.ctypes.data, roots.size, nh_words,
+                                        metric.ctypes.data, count.ctypes.data, nh.ctypes.data)
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+        return metric, count, nh
 
 
 class Multi:

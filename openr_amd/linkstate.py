@@ -564,6 +564,72 @@ class LinkState:
             raise LinkStateError(self._err())
         return metric, count, nh
 
+    @staticmethod
+    def _prefix_lines(prefixes: Dict[str, Sequence[str]]) -> List[str]:
+        lines = ["\t".join(a) for a in prefixes.values()]
+        for ln in lines:
+            if "\n" in ln:
+                raise ValueError("node names must not contain newlines")
+        return lines
+
+    def track_select(self, prefixes: Dict[str, Sequence[str]], use_link_metric: bool = True) -> None:
+        """odl_track_select: bind the LinkState to a prefix table (as
+        all_sources_select takes it) and store the current selection as the
+        baseline of select_delta, on the device."""
+        lines = self._prefix_lines(prefixes)
+        if self._L.odl_track_select(self._h, "\n".join(lines).encode(), len(lines),
+                                    int(use_link_metric)) != 0:
+            raise LinkStateError(self._err())
+        self._tracked_prefixes = len(lines)
+
+    def select_delta(self) -> dict:
+        """odl_select_delta: what changed in the tracked selection since the
+        last call (DecisionRouteDb::calculateUpdate) -> dict(changes =
+        structured array root / prefix / metric / count by node id with the
+        NEW values, nh = [n, W] u32 next-hop words, rebased = node ids whose
+        neighbour list changed (read them with select_tracked), full = True
+        when the node names changed and everything is to be read anew)."""
+        n, m, W, full = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int32()
+        pc, pn, pr = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        if self._L.odl_select_delta(self._h, C.byref(n), C.byref(m), C.byref(W), C.byref(full),
+                                    C.byref(pc), C.byref(pn), C.byref(pr)) != 0:
+            raise LinkStateError(self._err())
+        try:
+            def take(p, count, dtype):
+                if not count:
+                    return np.zeros(0, dtype)
+                nbytes = count * np.dtype(dtype).itemsize
+                return np.frombuffer(C.string_at(p, nbytes), dtype).copy()
+            from .engine import CHANGE_DTYPE
+            changes = take(pc, n.value, CHANGE_DTYPE)
+            nh = take(pn, n.value * W.value, np.uint32).reshape(n.value, W.value)
+            rebased = take(pr, m.value, np.uint32)
+        finally:
+            for p in (pc, pn, pr):
+                self._L.odl_free_buf(p)
+        return {"changes": changes, "nh": nh, "rebased": rebased, "full": bool(full.value)}
+
+    def select_tracked(self, nodes: Sequence[str], nh_words: int = 0):
+        """odl_select_tracked: the baseline of some nodes (names) ->
+        (metric [n, P], count [n, P], nh [n, P, W])."""
+        if not hasattr(self, "_tracked_prefixes"):
+            raise LinkStateError("select_tracked: no tracked table (track_select)")
+        P = self._tracked_prefixes
+        W = nh_words
+        if not W:
+            need = C.c_uint32(0)
+            if self._L.odl_all_sources_select(self._h, b"", 0, 1, 0, C.byref(need), None, None,
+                                              None) != 0:
+                raise LinkStateError(self._err())
+            W = int(need.value)
+        metric = np.zeros((len(nodes), P), np.uint32)
+        count = np.zeros((len(nodes), P), np.uint32)
+        nh = np.zeros((len(nodes), P, W), np.uint32)
+        if self._L.odl_select_tracked(self._h, "\n".join(nodes).encode(), len(nodes), W,
+                                      metric.ctypes.data, count.ctypes.data, nh.ctypes.data) != 0:
+            raise LinkStateError(self._err())
+        return metric, count, nh
+
     def next_hop_names(self, root, words, csr: Optional[Dict[str, np.ndarray]] = None,
                        names: Optional[Sequence[str]] = None) -> List[str]:
         """Names of the next hops in one (root, prefix) mask of

@@ -147,17 +147,20 @@ def metric_graph(links, overloaded=()):
             for i, nm in enumerate(sorted(adjs))]
 
 
-def furniture(at, island=2, tag="f"):
+def furniture(at, island=2, tag="f", unit=False):
     """(links, overloaded names) of what every limit shape carries besides
     its critical path, hung off node `at`: an ECMP diamond at -> {fa, fb} ->
     fc (3 either way, asymmetric per direction), an overloaded node fo on fa
     and fc (a destination, never a relay), a down link fa - fb, and an
-    island za - zb - ... of `island` nodes nothing else reaches."""
+    island za - zb - ... of `island` nodes nothing else reaches. unit: every
+    metric 1 (the diamond is 2 either way), for unit-metric shapes."""
     fa, fb, fc, fo = (tag + x for x in "abco")
     links = [(at, fa, 1, 2), (at, fb, 2, 1), (fa, fc, 2, 1), (fb, fc, 1, 2),
              (fa, fo, 1, 3), (fc, fo, 3, 1), (fa, fb, 1, 1, "down")]
     isl = [f"z{chr(97 + t)}" for t in range(island)]
     links += [(isl[t], isl[t + 1], 5 + t, 7 + t) for t in range(island - 1)]
+    if unit:
+        links = [ln[:2] + (1, 1) + ln[4:] for ln in links]
     return links, {fo}
 
 
@@ -172,3 +175,13 @@ def dist_bound(csr):
         row = [int(met[e]) for e in range(int(rp[u]), int(rp[u + 1])) if up[e]]
         total += max(row, default=0)
     return total
+
+
+def bundle(a, b, routes, hops, tag, w=1):
+    """links of `routes` edge-disjoint routes of `hops` links (metric w both
+    ways) from a to b over private nodes {tag}{route:03d}_{hop:03d}"""
+    links = []
+    for r in range(routes):
+        chain = [a] + [f"{tag}{r:03d}_{i:03d}" for i in range(1, hops)] + [b]
+        links += [(chain[i], chain[i + 1], w, w) for i in range(hops)]
+    return links

@@ -229,6 +229,39 @@ int odl_select_delta(odl_ls* ls, uint32_t* n_changes, uint32_t* n_rebased, uint3
                      int* full, void** changes, void** nh, void** rebased);
 int odl_select_tracked(odl_ls* ls, const char* nodes_nl, uint32_t n, uint32_t nh_words,
                        uint32_t* metric, uint32_t* count, uint32_t* nh);
+/* UCMP weights of every node for every prefix of the tracked table
+ * (LinkState::allSourcesUcmp): SpfSolver::getNodeUcmpResult ->
+ * resolveUcmpWeights (SpfSolver.cpp:1091-1161, LinkState.cpp:913-1033) for all
+ * nodes at once, resolved on the device over the selection odl_track_select /
+ * odl_select_delta keep resident (ospf_selstate_ucmp). algo 2 =
+ * SP_UCMP_ADJ_WEIGHT_PROPAGATION, 3 = SP_UCMP_PREFIX_WEIGHT_PROPAGATION.
+ * leaf_weights: one int64 >= 0 per announcer NAME of odl_track_select's lines,
+ * in their order (n_weights of them; for a name given twice the first counts).
+ * Outputs by node id: weight [V][P] (advertised; 0 unless OK) and status [V][P]
+ * (0 OK, 1 no announcer reached, 2 a zero-weight announcer among the min-cost
+ * ones: the reference returns nullopt, 3 a sum above 2^63 - 1 -- device only);
+ * *rounds = the device's gather rounds, *on_device = 1 when the device
+ * answered, *engine_ms = the engine call alone; any may be NULL. The tracked
+ * selection must be the current topology's (odl_track_select or
+ * odl_select_delta since the last change): -1 otherwise. On the host path
+ * (odl_set_host_spf, metrics outside the engine contract, several devices,
+ * after a device error with degrading on) the answer is the loop
+ * resolveUcmpWeights(getSpfResult(node), min-cost announcers) per node and
+ * prefix. odl_ucmp_tracked: the per-link view of n nodes (names, one per line)
+ * from that result: weight / status [n][P], off [n * P + 1] and *wt (malloc'd,
+ * *n_wt int64; odl_free_buf) -- entry (i, p)'s next-hop weights, one per
+ * selected next hop in the node's distinct-neighbour order, divided by their
+ * gcd; every tight link to that neighbour carries it. odl_ucmp_host_loop: the
+ * host loop alone for n nodes, same outputs, nothing kept (cross-checks and
+ * measurement). */
+int odl_all_sources_ucmp(odl_ls* ls, int algo, const int64_t* leaf_weights, uint32_t n_weights,
+                         int64_t* weight, uint8_t* status, uint32_t* rounds, int* on_device,
+                         double* engine_ms);
+int odl_ucmp_tracked(odl_ls* ls, const char* nodes_nl, uint32_t n, int64_t* weight, uint8_t* status,
+                     uint64_t* off, void** wt, uint64_t* n_wt);
+int odl_ucmp_host_loop(odl_ls* ls, int algo, const int64_t* leaf_weights, uint32_t n_weights,
+                       const char* nodes_nl, uint32_t n, int64_t* weight, uint8_t* status,
+                       uint64_t* off, void** wt, uint64_t* n_wt);
 /* Fill the getSpfResult memo for many roots with one engine batch. */
 int odl_spf_prefetch(odl_ls* ls, const char* roots_nl, uint32_t n, int use_link_metric);
 /* getKthPaths(src, d, 2) for every d, masked reruns batched on the engine;

@@ -714,6 +714,67 @@ int ospf_selstate_update(ospf_selstate* st, ospf_sweep* sw, uint32_t nh_words,
                          uint32_t cap_rebased, uint32_t* n_rebased);
 int ospf_selstate_copy(ospf_selstate* st, const uint32_t* roots, uint32_t n, uint32_t nh_words,
                        uint32_t* metric, uint32_t* count, uint32_t* nh);
+/* UCMP weights of every root and prefix, resolved on the device over the
+ * selection a primed state holds: SpfSolver::getNodeUcmpResult ->
+ * LinkState::resolveUcmpWeights (openr/decision/SpfSolver.cpp:1091-1161,
+ * LinkState.cpp:913-1033) for all roots at once, instead of a priority-queue
+ * walk per root and prefix. The weight a node advertises in any root's walk is
+ * that of its own selection (DESIGN.md §3 o'''):
+ *   W(u) = leaf weight                       u announces the prefix (metric 0)
+ *   W(u) = sum over u's selected next hops k of
+ *            c(u, k) * W(k)                  OSPF_UCMP_PREFIX
+ *            S(u, k)                         OSPF_UCMP_ADJ
+ * c(u, k) = the tight links u - k: up, at the smallest metric u advertises on
+ * an up link to k (every up link when the selection was swept under
+ * OSPF_HOP_COUNT); derived on the device from the loaded graph, in-place
+ * patches included. S(u, k) = the sum of u's link weights (getWeightFromNode)
+ * over those links: the engine holds no link weights, so the caller passes
+ * link_weight_sum, one per distinct-neighbour slot in the order of
+ * ospf_root_neighbors, node after node (n_slots of them: the count
+ * ospf_selstate_ucmp_info reports); NULL is allowed for OSPF_UCMP_PREFIX.
+ * leaf_weight is parallel to the table's `nodes` (one per announcer entry).
+ *   ospf_selstate_ucmp       resolves W and a status for every (node, prefix)
+ *                            and keeps them resident; *rounds = gather rounds
+ *                            taken = the hop depth of the deepest selected path.
+ *   ospf_selstate_ucmp_copy  the per-link view of some roots: advertised
+ *                            [n][P], status [n][P], and a CSR off [n * P + 1] /
+ *                            wt of the root's next-hop weights -- one per set
+ *                            next-hop bit of the entry, in bit order, W(k)
+ *                            divided by the gcd of the entry's weights when it
+ *                            is > 1 (normalizeNextHopWeights, LinkState.h:
+ *                            317-328); every tight link to k carries wt. An
+ *                            entry that is not OSPF_UCMP_OK has advertised 0
+ *                            and no weights.
+ *                            off NULL: advertised and status only (wt, cap
+ *                            ignored, *n_wt = 0).
+ * Status: OK; NONE no announcer reached; VOID a zero-weight announcer among
+ * the min-cost ones (getNodeUcmpResult returns nullopt, :1139-1142; it
+ * propagates to every node that selects through it); OVERFLOW a sum above
+ * 2^63 - 1 (propagates likewise; VOID wins over OVERFLOW). An entry is OK only when
+ * its advertised weight AND its next hops' weights are representable, so under
+ * OSPF_UCMP_ADJ too an OVERFLOW next hop marks the entry (deliberate).
+ * OSPF_E_INVAL, nothing changed: a state not primed; a graph version other
+ * than the one the state's selection was stored on (reload or patch without
+ * ospf_selstate_update); a negative weight; OSPF_UCMP_ADJ without
+ * link_weight_sum; n_slots that does not match; copy before a run, or after
+ * the selection changed (update) without a new run. copy with more weights
+ * than `cap`: OSPF_E_RANGE, *n_wt = the count needed, no output written. Any
+ * failure (an injected one included) leaves the previous result as it was.
+ * Several parts / ospf_msweep are not supported (as the state). */
+#define OSPF_UCMP_ADJ 2u    /* SP_UCMP_ADJ_WEIGHT_PROPAGATION */
+#define OSPF_UCMP_PREFIX 3u /* SP_UCMP_PREFIX_WEIGHT_PROPAGATION */
+#define OSPF_UCMP_OK 0u
+#define OSPF_UCMP_NONE 1u
+#define OSPF_UCMP_VOID 2u
+#define OSPF_UCMP_OVERFLOW 3u
+int ospf_selstate_ucmp(ospf_selstate* st, uint32_t algo, const int64_t* leaf_weight,
+                       const int64_t* link_weight_sum, uint32_t n_slots, uint32_t* rounds);
+int ospf_selstate_ucmp_copy(ospf_selstate* st, const uint32_t* roots, uint32_t n,
+                            int64_t* advertised, uint8_t* status, uint64_t* off, int64_t* wt,
+                            uint64_t cap, uint64_t* n_wt);
+/* rounds of the last run (0: none yet) and the graph's distinct-neighbour
+ * slots (the length of link_weight_sum); either may be NULL */
+int ospf_selstate_ucmp_info(const ospf_selstate* st, uint32_t* rounds, uint32_t* n_slots);
 /* Time every launch unit alone on its stream: reps (>= 1) timed launches
  * after one untimed one; fills min(cap, n_launches) records. The sweep must
  * have run once. */
@@ -778,7 +839,8 @@ uint64_t ospf_spf_runs(const ospf_ctx* ctx);
  * ospf_load_graph / ospf_sssp_batch / ospf_ksp2_run / ospf_sweep_create /
  * ospf_sweep_run / ospf_sweep_copy_rows / ospf_sweep_select_dev /
  * ospf_sweep_select / ospf_msweep_select (per part) / ospf_selstate_prime /
- * ospf_selstate_update / ospf_selstate_copy on this context fails with
+ * ospf_selstate_update / ospf_selstate_copy / ospf_selstate_ucmp /
+ * ospf_selstate_ucmp_copy on this context fails with
  * OSPF_E_DEVICE and does nothing (0 = off). Lets the caller's handling of a
  * device error be tested without a faulting GPU. */
 int ospf_inject_error(ospf_ctx* ctx, uint32_t after_calls);

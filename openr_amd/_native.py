@@ -43,6 +43,7 @@ ENGINE_SYMBOLS = [
     "ospf_sweep_select_dev", "ospf_sweep_select", "ospf_msweep_select",
     "ospf_selstate_create", "ospf_selstate_destroy", "ospf_selstate_last_error",
     "ospf_selstate_device_bytes", "ospf_selstate_prime", "ospf_selstate_update", "ospf_selstate_copy",
+    "ospf_selstate_ucmp", "ospf_selstate_ucmp_copy", "ospf_selstate_ucmp_info",
     "ospf_multi_open", "ospf_multi_close", "ospf_multi_last_error", "ospf_multi_size",
     "ospf_multi_ctx", "ospf_multi_load_graph", "ospf_msweep_create", "ospf_msweep_destroy",
     "ospf_msweep_run", "ospf_msweep_digests", "ospf_msweep_part", "ospf_msweep_owner",
@@ -58,6 +59,7 @@ DECISION_SYMBOLS = [
     "odl_last_decode_error", "odl_get_counters", "odl_last_engine_error", "odl_inject_engine_error",
     "odl_set_degrade", "odl_all_sources_select",
     "odl_track_select", "odl_select_delta", "odl_select_tracked",
+    "odl_all_sources_ucmp", "odl_ucmp_tracked", "odl_ucmp_host_loop",
 ]
 
 
@@ -227,6 +229,9 @@ def engine() -> C.CDLL:
         L.ospf_selstate_update.argtypes = [vp, vp, u32, vp, vp, u32, C.POINTER(u32), vp, u32,
                                            C.POINTER(u32)]
         L.ospf_selstate_copy.argtypes = [vp, vp, u32, u32, vp, vp, vp]
+        L.ospf_selstate_ucmp.argtypes = [vp, u32, vp, vp, u32, C.POINTER(u32)]
+        L.ospf_selstate_ucmp_copy.argtypes = [vp, vp, u32, vp, vp, vp, vp, u64, C.POINTER(u64)]
+        L.ospf_selstate_ucmp_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
         L.ospf_sweep_profile.argtypes = [vp, u32, vp, u32]
         L.ospf_sweep_graph_memsets.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.ospf_multi_open.argtypes = [vp, u32, C.POINTER(vp)]
@@ -267,6 +272,11 @@ def decision() -> C.CDLL:
         L.odl_select_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
                                        C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.odl_select_tracked.argtypes = [vp, cp, u32, u32, vp, vp, vp]
+        L.odl_all_sources_ucmp.argtypes = [vp, i32, vp, u32, vp, vp, C.POINTER(u32), C.POINTER(i32),
+                                           C.POINTER(C.c_double)]
+        L.odl_ucmp_tracked.argtypes = [vp, cp, u32, vp, vp, vp, C.POINTER(vp), C.POINTER(u64)]
+        L.odl_ucmp_host_loop.argtypes = [vp, i32, vp, u32, cp, u32, vp, vp, vp, C.POINTER(vp),
+                                         C.POINTER(u64)]
         L.odl_sweep_stats.argtypes = [vp, vp]
         L.odl_sweep_stats.restype = None
         L.odl_destroy.argtypes = [vp]

@@ -480,6 +480,66 @@ int odl_select_tracked(odl_ls* h, const char* nodes_nl, uint32_t n, uint32_t nh_
   }, -1);
 }
 
+namespace {
+// flat leaf weights -> one list per tracked prefix (parallel to odl_track_select's names)
+std::vector<std::vector<int64_t>> leafLists(const odl::LinkState& ls, const int64_t* w, uint32_t n) {
+  size_t total = 0;
+  for (const auto& p : ls.trackedPrefixes()) total += p.size();
+  if (total != n || (n && !w))
+    throw std::invalid_argument("leaf weights: " + std::to_string(n) + " given for " +
+                                std::to_string(total) + " announcer names of the tracked table");
+  std::vector<std::vector<int64_t>> out;
+  for (const auto& p : ls.trackedPrefixes()) {
+    out.emplace_back(w, w + p.size());
+    w += p.size();
+  }
+  return out;
+}
+
+int giveView(const odl::LinkState::UcmpView& v, int64_t* weight, uint8_t* status, uint64_t* off,
+             void** wt, uint64_t* n_wt) {
+  if (!wt || !n_wt) throw std::invalid_argument("null output pointer");
+  *wt = dupVec(v.wt);
+  *n_wt = v.wt.size();
+  if (weight) std::copy(v.weight.begin(), v.weight.end(), weight);
+  if (status) std::copy(v.status.begin(), v.status.end(), status);
+  if (off) std::copy(v.off.begin(), v.off.end(), off);
+  return 0;
+}
+}  // namespace
+
+int odl_all_sources_ucmp(odl_ls* h, int algo, const int64_t* leaf_weights, uint32_t n_weights,
+                         int64_t* weight, uint8_t* status, uint32_t* rounds, int* on_device,
+                         double* engine_ms) {
+  return guard(h, [&]() -> int {
+    const auto r = h->ls.allSourcesUcmp((odl::UcmpAlgo)algo, leafLists(h->ls, leaf_weights, n_weights));
+    if (weight) std::copy(r.weight.begin(), r.weight.end(), weight);
+    if (status) std::copy(r.status.begin(), r.status.end(), status);
+    if (rounds) *rounds = r.rounds;
+    if (on_device) *on_device = r.device ? 1 : 0;
+    if (engine_ms) *engine_ms = r.engineMs;
+    return 0;
+  }, -1);
+}
+
+int odl_ucmp_tracked(odl_ls* h, const char* nodes_nl, uint32_t n, int64_t* weight, uint8_t* status,
+                     uint64_t* off, void** wt, uint64_t* n_wt) {
+  return guard(h, [&]() -> int {
+    return giveView(h->ls.ucmpTracked(splitNl(nodes_nl ? nodes_nl : "", n)), weight, status, off, wt,
+                    n_wt);
+  }, -1);
+}
+
+int odl_ucmp_host_loop(odl_ls* h, int algo, const int64_t* leaf_weights, uint32_t n_weights,
+                       const char* nodes_nl, uint32_t n, int64_t* weight, uint8_t* status,
+                       uint64_t* off, void** wt, uint64_t* n_wt) {
+  return guard(h, [&]() -> int {
+    return giveView(h->ls.ucmpHostLoop((odl::UcmpAlgo)algo, leafLists(h->ls, leaf_weights, n_weights),
+                                       splitNl(nodes_nl ? nodes_nl : "", n)),
+                    weight, status, off, wt, n_wt);
+  }, -1);
+}
+
 int odl_all_sources_prefetch(odl_ls* h, int use_link_metric) {
   return guard(h, [&]() -> int {
     h->ls.prefetchAllSources(use_link_metric != 0);

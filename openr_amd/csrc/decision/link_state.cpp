@@ -1246,6 +1246,7 @@ void LinkState::trackDropDev() {
   if (selstate_) ospf_selstate_destroy(selstate_);
   selstate_ = nullptr;
   trackDev_ = false;
+  ucmpDev_ = false;
 }
 
 void LinkState::trackPull() {
@@ -1299,6 +1300,7 @@ void LinkState::trackPrime() {
   trackWords_ = W;
   trackNbrs_.resize(V);
   for (uint32_t v = 0; v < V; ++v) trackNbrs_[v] = nbrsOf(v);
+  trackVersion_ = snapVersion_;
 }
 
 void LinkState::trackSelect(const std::vector<std::vector<std::string>>& prefixes,
@@ -1378,6 +1380,7 @@ LinkState::SelectDelta LinkState::selectDeltaImpl() {
   }
   trackWords_ = W;
   for (uint32_t v : out.rebased) trackNbrs_[v] = nbrsOf(v);
+  trackVersion_ = snapVersion_;
   return out;
 }
 
@@ -1422,6 +1425,219 @@ LinkState::SelectResult LinkState::selectTracked(const std::vector<std::string>&
     }
     return r;
   });
+}
+
+// ---------------------------------------------------------------- allSourcesUcmp
+void LinkState::trackCurrent(const char* who) {
+  if (!tracking_) throw std::logic_error(std::string(who) + ": no tracked table (trackSelect)");
+  snapshot();
+  if (snapVersion_ != trackVersion_ || csr_->names != trackNames_ || (!trackDev_ && !trackHostOk_))
+    throw std::logic_error(std::string(who) +
+                           ": the tracked selection is older than the topology (selectDelta)");
+}
+
+std::vector<std::vector<int64_t>> LinkState::trackLeafWeights(
+    const std::vector<std::vector<uint32_t>>& ann,
+    const std::vector<std::vector<int64_t>>& leafWeights) const {
+  if (leafWeights.size() != trackPrefixes_.size())
+    throw std::invalid_argument("allSourcesUcmp: one weight list per tracked prefix");
+  std::vector<std::vector<int64_t>> out(ann.size());
+  for (size_t p = 0; p < ann.size(); ++p) {
+    if (leafWeights[p].size() != trackPrefixes_[p].size())
+      throw std::invalid_argument("allSourcesUcmp: one weight per announcer name of prefix " +
+                                  std::to_string(p));
+    std::unordered_map<uint32_t, int64_t> by;  // the first weight given for an id
+    for (size_t i = 0; i < trackPrefixes_[p].size(); ++i) {
+      if (leafWeights[p][i] < 0) throw std::invalid_argument("allSourcesUcmp: a negative weight");
+      const auto it = csr_->ids.find(trackPrefixes_[p][i]);
+      if (it != csr_->ids.end()) by.emplace(it->second, leafWeights[p][i]);
+    }
+    for (uint32_t a : ann[p]) out[p].push_back(by.at(a));
+  }
+  return out;
+}
+
+std::vector<uint32_t> LinkState::trackIds(const std::vector<std::string>& nodes, const char* who) const {
+  std::vector<uint32_t> ids;
+  for (const auto& nm : nodes) {
+    const auto it = std::lower_bound(trackNames_.begin(), trackNames_.end(), nm);
+    if (it == trackNames_.end() || *it != nm)
+      throw std::invalid_argument(std::string(who) + ": unknown node " + nm);
+    ids.push_back((uint32_t)(it - trackNames_.begin()));
+  }
+  return ids;
+}
+
+LinkState::UcmpView LinkState::ucmpHostImpl(UcmpAlgo algo, const std::vector<std::vector<uint32_t>>& ann,
+                                            const std::vector<std::vector<int64_t>>& w,
+                                            const std::vector<uint32_t>& ids) {
+  const size_t P = ann.size();
+  UcmpView out;
+  out.prefixes = (uint32_t)P;
+  out.weight.assign(ids.size() * P, 0);
+  out.status.assign(ids.size() * P, OSPF_UCMP_NONE);
+  out.off.assign(ids.size() * P + 1, 0);
+  for (size_t i = 0; i < ids.size(); ++i) {
+    const std::string& me = csr_->names[ids[i]];
+    const SpfResult& res = getSpfResult(me, trackMetric_);
+    const std::vector<uint32_t> nbrs = nbrsOf(ids[i]);
+    for (size_t p = 0; p < P; ++p) {
+      const size_t e = i * P + p;
+      out.off[e + 1] = out.wt.size();
+      // the min-cost announcers (getNextHopsWithMetric) and their weights
+      Metric shortest = std::numeric_limits<Metric>::max();
+      std::unordered_map<std::string, int64_t> leaves;
+      bool zero = false;
+      for (size_t k = 0; k < ann[p].size(); ++k) {
+        const auto it = res.find(csr_->names[ann[p][k]]);
+        if (it == res.end()) continue;
+        const Metric d = it->second.metric();
+        if (d > shortest) continue;
+        if (d < shortest) {
+          shortest = d;
+          leaves.clear();
+          zero = false;
+        }
+        leaves.emplace(csr_->names[ann[p][k]], w[p][k]);
+        zero |= w[p][k] == 0;
+      }
+      if (leaves.empty()) continue;
+      if (zero) {  // getNodeUcmpResult returns nullopt (SpfSolver.cpp:1139-1142)
+        out.status[e] = OSPF_UCMP_VOID;
+        continue;
+      }
+      const UcmpResult all = resolveUcmpWeights(res, leaves, algo, trackMetric_);
+      const auto mine = all.find(me);
+      if (mine == all.end()) continue;
+      out.status[e] = OSPF_UCMP_OK;
+      out.weight[e] = mine->second.weight().value_or(0);
+      std::map<uint32_t, int64_t> byNbr;  // every tight link to a neighbour carries its weight
+      for (const auto& kv : mine->second.nextHopLinks())
+        byNbr.emplace(csr_->ids.at(kv.second.nextHopNode), kv.second.weight);
+      for (uint32_t k : nbrs) {
+        const auto it = byNbr.find(k);
+        if (it != byNbr.end()) out.wt.push_back(it->second);
+      }
+      out.off[e + 1] = out.wt.size();
+    }
+  }
+  return out;
+}
+
+LinkState::UcmpAll LinkState::allSourcesUcmp(UcmpAlgo algo,
+                                             const std::vector<std::vector<int64_t>>& leafWeights) {
+  if (algo != UcmpAlgo::kAdjWeightPropagation && algo != UcmpAlgo::kPrefixWeightPropagation)
+    throw std::invalid_argument("allSourcesUcmp: not a UCMP algorithm");
+  trackCurrent("allSourcesUcmp");
+  const auto ann = trackAnn();
+  const auto w = trackLeafWeights(ann, leafWeights);
+  return guarded([&] {
+    const size_t V = csr_->names.size(), P = ann.size();
+    UcmpAll out;
+    out.prefixes = (uint32_t)P;
+    ucmpDev_ = ucmpHostOk_ = false;
+    if (trackDev_ && !hostRun(trackMetric_) && devices_.size() == 1) {
+      std::vector<int64_t> flat;
+      for (const auto& l : w) flat.insert(flat.end(), l.begin(), l.end());
+      // S per (node, distinct neighbour): the node's link weights over the
+      // tight links (up, at the smallest metric towards the neighbour; every
+      // up link under hop count), slots in nbrsOf order, node after node
+      std::vector<int64_t> S;
+      for (uint32_t u = 0; u < V; ++u) {
+        uint32_t e = csr_->rowPtr[u];
+        const uint32_t hi = csr_->rowPtr[u + 1];
+        while (e < hi) {
+          const uint32_t k = csr_->col[e];
+          uint32_t best = std::numeric_limits<uint32_t>::max();
+          int64_t sum = 0;
+          for (; e < hi && csr_->col[e] == k; ++e) {
+            if (!csr_->edgeUp[e]) continue;
+            const uint32_t m = trackMetric_ ? csr_->metric[e] : 1u;
+            if (m > best) continue;
+            if (m < best) {
+              best = m;
+              sum = 0;
+            }
+            sum += csr_->links.at(csr_->linkId[e])->weightFrom(csr_->names[u]);
+          }
+          if (k != u) S.push_back(sum);
+        }
+      }
+      const auto t0 = std::chrono::steady_clock::now();
+      const int rc = ospf_selstate_ucmp(selstate_, (uint32_t)algo, flat.data(), S.data(),
+                                        (uint32_t)S.size(), &out.rounds);
+      out.engineMs =
+          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      if (rc != OSPF_OK) throw EngineError(rc, ospf_selstate_last_error(selstate_));
+      out.weight.assign(V * P, 0);
+      out.status.assign(V * P, OSPF_UCMP_NONE);
+      std::vector<uint32_t> ids(V);
+      for (uint32_t v = 0; v < V; ++v) ids[v] = v;
+      uint64_t n = 0;
+      const int rc2 = ospf_selstate_ucmp_copy(selstate_, ids.data(), (uint32_t)V, out.weight.data(),
+                                              out.status.data(), nullptr, nullptr, 0, &n);
+      if (rc2 != OSPF_OK) throw EngineError(rc2, ospf_selstate_last_error(selstate_));
+      out.device = true;
+      ucmpDev_ = true;
+    } else {
+      std::vector<uint32_t> ids(V);
+      for (uint32_t v = 0; v < V; ++v) ids[v] = v;
+      ucmpHost_ = ucmpHostImpl(algo, ann, w, ids);
+      ucmpHostOk_ = true;
+      out.weight = ucmpHost_.weight;
+      out.status = ucmpHost_.status;
+    }
+    ucmpVersion_ = trackVersion_;
+    return out;
+  });
+}
+
+LinkState::UcmpView LinkState::ucmpHostLoop(UcmpAlgo algo,
+                                            const std::vector<std::vector<int64_t>>& leafWeights,
+                                            const std::vector<std::string>& nodes) {
+  trackCurrent("ucmpHostLoop");
+  const auto ann = trackAnn();
+  const auto w = trackLeafWeights(ann, leafWeights);
+  const auto ids = trackIds(nodes, "ucmpHostLoop");
+  return guarded([&] { return ucmpHostImpl(algo, ann, w, ids); });
+}
+
+LinkState::UcmpView LinkState::ucmpTracked(const std::vector<std::string>& nodes) {
+  trackCurrent("ucmpTracked");
+  if ((!ucmpDev_ && !ucmpHostOk_) || ucmpVersion_ != trackVersion_)
+    throw std::logic_error("ucmpTracked: no UCMP result of the tracked selection (allSourcesUcmp)");
+  const auto ids = trackIds(nodes, "ucmpTracked");
+  const size_t n = ids.size(), P = trackPrefixes_.size();
+  UcmpView r;
+  r.prefixes = (uint32_t)P;
+  r.weight.assign(n * P, 0);
+  r.status.assign(n * P, OSPF_UCMP_NONE);
+  r.off.assign(n * P + 1, 0);
+  if (ucmpDev_) {
+    // a device error here is not degraded: the result lives on the device
+    // only, so the caller resolves again (allSourcesUcmp, which degrades)
+    uint64_t need = 0;
+    for (uint64_t cap = 1024;;) {
+      r.wt.assign(cap, 0);
+      const int rc = ospf_selstate_ucmp_copy(selstate_, ids.data(), (uint32_t)n, r.weight.data(),
+                                             r.status.data(), r.off.data(), r.wt.data(), cap, &need);
+      if (rc == OSPF_OK) break;
+      if (rc != OSPF_E_RANGE) throw EngineError(rc, ospf_selstate_last_error(selstate_));
+      cap = need;  // nothing was written: the same call, large enough
+    }
+    r.wt.resize(need);
+    return r;
+  }
+  const UcmpView& h = ucmpHost_;
+  for (size_t i = 0; i < n; ++i)
+    for (size_t p = 0; p < P; ++p) {
+      const size_t s = (size_t)ids[i] * P + p;
+      r.weight[i * P + p] = h.weight[s];
+      r.status[i * P + p] = h.status[s];
+      r.wt.insert(r.wt.end(), h.wt.begin() + h.off[s], h.wt.begin() + h.off[s + 1]);
+      r.off[i * P + p + 1] = r.wt.size();
+    }
+  return r;
 }
 
 void LinkState::evictSpf(const std::vector<std::string>& roots, bool useLinkMetric) {

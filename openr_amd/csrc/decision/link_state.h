@@ -591,6 +591,46 @@ class LinkState {
   void trackSelect(const std::vector<std::vector<std::string>>& prefixes, bool useLinkMetric = true);
   SelectDelta selectDelta();
   SelectResult selectTracked(const std::vector<std::string>& nodes, uint32_t nhWords = 0);
+  // UCMP weights of every node for every prefix of the tracked table:
+  // SpfSolver::getNodeUcmpResult -> resolveUcmpWeights (SpfSolver.cpp:1091-1161,
+  // LinkState.cpp:913-1033) for all nodes at once. leafWeights is parallel to
+  // trackSelect's prefixes (one weight per announcer name, >= 0; for a name
+  // given twice the first counts). On the device (ospf_selstate_ucmp over the
+  // resident selection; S(u, k) summed here from the Links' weightFrom) the
+  // result stays resident and ucmpTracked reads some nodes' per-link view
+  // (ospf_selstate_ucmp_copy); on the host path (setHostSpf, metrics outside
+  // the engine contract, a multi-device LinkState, after a device error) it is
+  // the loop resolveUcmpWeights(getSpfResult(node), min-cost announcers) per
+  // node and prefix, kept on the host. The tracked selection must be the
+  // current topology's (trackSelect / selectDelta since the last change):
+  // std::logic_error otherwise. status: OSPF_UCMP_OK / NONE (no announcer
+  // reached) / VOID (a zero-weight announcer among the min-cost ones) /
+  // OVERFLOW (device only: the host loop adds as the reference does).
+  struct UcmpAll {
+    uint32_t prefixes = 0, rounds = 0;
+    bool device = false;
+    double engineMs = 0;           // the ospf_selstate_ucmp call alone
+    std::vector<int64_t> weight;   // [V][prefixes] advertised, 0 unless OK
+    std::vector<uint8_t> status;   // [V][prefixes]
+  };
+  // per-link view of n nodes: entry (i, p)'s next-hop weights are
+  // wt[off[i * P + p] .. off[i * P + p + 1]), one per selected next hop in the
+  // node's distinct-neighbour order, gcd-normalised; every tight link to that
+  // neighbour carries it
+  struct UcmpView {
+    uint32_t prefixes = 0;
+    std::vector<int64_t> weight;
+    std::vector<uint8_t> status;
+    std::vector<uint64_t> off;
+    std::vector<int64_t> wt;
+  };
+  UcmpAll allSourcesUcmp(UcmpAlgo algo, const std::vector<std::vector<int64_t>>& leafWeights);
+  UcmpView ucmpTracked(const std::vector<std::string>& nodes);
+  const std::vector<std::vector<std::string>>& trackedPrefixes() const { return trackPrefixes_; }
+  // the host loop alone for some nodes (what allSourcesUcmp degrades to): for
+  // cross-checks and measurement; keeps nothing
+  UcmpView ucmpHostLoop(UcmpAlgo algo, const std::vector<std::vector<int64_t>>& leafWeights,
+                        const std::vector<std::string>& nodes);
   bool isMemoised(const std::string& root, bool useLinkMetric) const {
     return (useLinkMetric ? memoMetric_ : memoHops_).count(root) > 0;
   }
@@ -822,6 +862,19 @@ class LinkState {
   void trackPull();   // the device baseline into trackHost_ (before the engine goes)
   void trackDropDev();
   SelectDelta selectDeltaImpl();
+  // ---- allSourcesUcmp ----
+  uint64_t trackVersion_ = 0;  // snapVersion_ of the tracked selection
+  bool ucmpDev_ = false;       // the result is the device state's
+  bool ucmpHostOk_ = false;    // the result is ucmpHost_ (every node)
+  uint64_t ucmpVersion_ = 0;   // trackVersion_ it was resolved on
+  UcmpView ucmpHost_;
+  std::vector<std::vector<int64_t>> trackLeafWeights(
+      const std::vector<std::vector<uint32_t>>& ann,
+      const std::vector<std::vector<int64_t>>& leafWeights) const;
+  std::vector<uint32_t> trackIds(const std::vector<std::string>& nodes, const char* who) const;
+  void trackCurrent(const char* who);
+  UcmpView ucmpHostImpl(UcmpAlgo algo, const std::vector<std::vector<uint32_t>>& ann,
+                        const std::vector<std::vector<int64_t>>& w, const std::vector<uint32_t>& ids);
   const std::vector<Path>& getKthPathsImpl(const std::string& src, const std::string& dst, size_t k);
   void prefetchKsp2Impl(const std::string& src, const std::vector<std::string>& dsts);
   bool hostRun(bool useLinkMetric) const { return hostOnly_ || (useLinkMetric && hostMetric_); }

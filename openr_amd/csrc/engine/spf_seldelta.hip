@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "spf_select_dev.h"
+#include "spf_selstate.h"
 #include "sweep_impl.h"
 
 namespace {
@@ -232,80 +233,17 @@ __global__ __launch_bounds__(256) void seldelta_kernel(const SdArgs a) {
 
 }  // namespace
 
-// ---------------------------------------------------------------- the state
-struct ospf_selstate {
-  ospf_ctx* c = nullptr;
-  std::string err;
-  uint32_t V = 0, P = 0;
-  std::vector<uint32_t> t_off, t_nodes;  // the table's copy
-  uint32_t* d_tab = nullptr;             // offsets, then nodes
-  bool primed = false;
-  int cur = 0;  // the committed buffer
-  struct Buf {
-    uint32_t* data = nullptr;  // the root blocks
-    size_t data_words = 0;     // allocated
-    uint64_t* off = nullptr;   // [V] block offset (words) by node id
-    uint32_t* w = nullptr;     // [V] next-hop words by node id
-    uint32_t* dn_off = nullptr;  // [V + 1]
-    uint32_t* dn = nullptr;
-    size_t dn_words = 0;  // allocated
-    std::vector<uint64_t> h_off;
-    std::vector<uint32_t> h_w;
-  } b[2];
-  uint32_t* d_roots = nullptr;  // [V]
-  uint32_t* d_cnt = nullptr;    // [2]
-  uint4* d_chg = nullptr;
-  uint32_t* d_chg_nh = nullptr;
-  uint32_t* d_reb = nullptr;
-  size_t chg_cap = 0, chg_nh_words = 0, reb_cap = 0;
-  uint64_t device_bytes = 0;
-};
-
 namespace {
 
 using namespace ospf_int;
 using namespace ospf_int::sweep;
-
-int stfail(ospf_selstate* st, int code, const std::string& m) {
-  st->err = m;
-  if (st->c) st->c->err = m;
-  return code;
-}
-
-#define STCHK(st, call)                                                               \
-  do {                                                                                \
-    hipError_t e_ = (call);                                                           \
-    if (e_ != hipSuccess)                                                             \
-      return stfail(st, OSPF_E_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-void dfree(ospf_selstate* st, void* p, size_t bytes) {
-  if (!p) return;
-  (void)hipFree(p);
-  st->device_bytes -= std::min<uint64_t>(st->device_bytes, bytes);
-}
-
-// *p grown to `count` elements (contents dropped); `have` = its capacity
-template <class T>
-int grow(ospf_selstate* st, T** p, size_t* have, size_t count) {
-  count = std::max<size_t>(count, 1);
-  if (*p && *have >= count) return OSPF_OK;
-  dfree(st, *p, *have * sizeof(T));
-  *p = nullptr;
-  *have = 0;
-  void* q = nullptr;
-  if (dev_malloc(st->c, &q, count * sizeof(T)) != hipSuccess)
-    return stfail(st, OSPF_E_NOMEM, "selstate: hipMalloc of " + std::to_string(count * sizeof(T)) + " B");
-  *p = (T*)q;
-  *have = count;
-  st->device_bytes += count * sizeof(T);
-  return OSPF_OK;
-}
+using namespace ospf_int::selst;
 
 void release(ospf_selstate* st) {
   if (!st->c) return;
   (void)hipSetDevice(st->c->device);
   (void)hipDeviceSynchronize();
+  if (st->release_ucmp) st->release_ucmp(st);
   for (auto& b : st->b) {
     (void)hipFree(b.data);
     (void)hipFree(b.off);
@@ -414,6 +352,13 @@ const char* sweep_error(const ospf_selstate* st, const ospf_sweep* sw) {
   return nullptr;
 }
 
+// the committed selection is sw's: what a consumer of the state checks it by
+void committed(ospf_selstate* st, const ospf_sweep* sw) {
+  st->gen = sw->gen;
+  st->hop = (sw->opts.flags & OSPF_HOP_COUNT) != 0;
+  ++st->serial;
+}
+
 uint32_t max_words(const ospf_sweep* sw) {
   uint32_t mw = 0;
   for (uint32_t r : sw->roots) mw = std::max(mw, sw->row_w[r]);
@@ -500,6 +445,7 @@ int ospf_selstate_prime(ospf_selstate* st, ospf_sweep* sw) {
   if (rc) return rc;
   st->cur ^= 1;
   st->primed = true;
+  committed(st, sw);
   return OSPF_OK;
 }
 
@@ -535,6 +481,7 @@ int ospf_selstate_update(ospf_selstate* st, ospf_sweep* sw, uint32_t nh_words,
   if (counts[1])
     STCHK(st, hipMemcpy(rebased_roots, st->d_reb, (size_t)counts[1] * 4, hipMemcpyDeviceToHost));
   st->cur ^= 1;  // commit
+  committed(st, sw);
   return OSPF_OK;
 }
 

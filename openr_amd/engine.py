@@ -459,6 +459,19 @@ class SelStateOverflow(EngineError):
         self.n_rebased = n_rebased
 
 
+class UcmpOverflow(EngineError):
+    """ospf_selstate_ucmp_copy's OSPF_E_RANGE (-4): more next-hop weights than
+    the capacity; nothing was written. n_wt is the count to retry with."""
+
+    def __init__(self, msg: str, n_wt: int):
+        super().__init__(-4, msg)
+        self.n_wt = n_wt
+
+
+UCMP_ALGOS = {"adj": 2, "prefix": 3}  # OSPF_UCMP_ADJ / OSPF_UCMP_PREFIX
+UCMP_OK, UCMP_NONE, UCMP_VOID, UCMP_OVERFLOW = 0, 1, 2, 3
+
+
 class SelState:
     """ospf_selstate: the selection of one prefix table for every root, kept
     on the device in each root's own width, and the entries a later sweep
@@ -533,6 +546,61 @@ class SelState:
         if rc != 0:
             raise EngineError(rc, self._msg())
         return metric, count, nh
+
+
+    # ------------------------------------------------------------ UCMP
+    @property
+    def ucmp_slots(self) -> int:
+        """Distinct-neighbour slots of the loaded graph: the length of
+        ucmp()'s link_weight_sum (ospf_root_neighbors order, node after node)."""
+        n = C.c_uint32()
+        self._L.ospf_selstate_ucmp_info(self._h, None, C.byref(n))
+        return int(n.value)
+
+    def ucmp(self, algo: str, leaf_weight: Sequence[int],
+             link_weight_sum: Optional[Sequence[int]] = None) -> int:
+        """ospf_selstate_ucmp: resolve the UCMP weight and status of every
+        (node, prefix) over the stored selection and keep them on the device
+        -> gather rounds taken (the hop depth of the deepest selected path).
+        algo 'adj' | 'prefix'; leaf_weight parallel to the table's nodes;
+        link_weight_sum one i64 per distinct-neighbour slot ('adj' needs it)."""
+        lw = np.ascontiguousarray(leaf_weight, np.int64)
+        ls = None if link_weight_sum is None else np.ascontiguousarray(link_weight_sum, np.int64)
+        rounds = C.c_uint32()
+        rc = self._L.ospf_selstate_ucmp(self._h, UCMP_ALGOS[algo], lw.ctypes.data if lw.size else None,
+                                        None if ls is None else ls.ctypes.data,
+                                        0 if ls is None else ls.size, C.byref(rounds))
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+        return int(rounds.value)
+
+    def ucmp_copy(self, roots: Sequence[int], cap: Optional[int] = None):
+        """ospf_selstate_ucmp_copy: the per-link view of `roots` (node ids) ->
+        (advertised [n, P] i64, status [n, P] u8, off [n * P + 1] u64, wt i64):
+        entry (i, p)'s normalised next-hop weights are wt[off[i * P + p] :
+        off[i * P + p + 1]], one per set next-hop bit in bit order. cap None:
+        retried once with the count the engine reports; else UcmpOverflow
+        (code -4, n_wt attached) when the weights do not fit."""
+        roots = np.ascontiguousarray(roots, np.uint32)
+        n = roots.size
+        adv = np.zeros((n, self.P), np.int64)
+        status = np.zeros((n, self.P), np.uint8)
+        off = np.zeros(n * self.P + 1, np.uint64)
+        need = C.c_uint64()
+        room = 1024 if cap is None else cap
+        while True:
+            wt = np.zeros(max(1, room), np.int64)
+            rc = self._L.ospf_selstate_ucmp_copy(self._h, roots.ctypes.data, n, adv.ctypes.data,
+                                                 status.ctypes.data, off.ctypes.data, wt.ctypes.data,
+                                                 room, C.byref(need))
+            if rc == -4 and cap is None and int(need.value) > room:
+                room = int(need.value)
+                continue
+            if rc == -4:
+                raise UcmpOverflow(self._msg(), int(need.value))
+            if rc != 0:
+                raise EngineError(rc, self._msg())
+            return adv, status, off, wt[: int(need.value)]
 
 
 class Multi:

@@ -630,6 +630,70 @@ class LinkState:
             raise LinkStateError(self._err())
         return metric, count, nh
 
+    def _leaf_weights(self, weights) -> np.ndarray:
+        lists = list(weights.values()) if isinstance(weights, dict) else list(weights)
+        if len(lists) != getattr(self, "_tracked_prefixes", -1):
+            raise LinkStateError("UCMP: one weight list per tracked prefix (track_select)")
+        return np.ascontiguousarray([int(w) for ws in lists for w in ws], np.int64)
+
+    def all_sources_ucmp(self, weights, algo: str = "prefix"):
+        """odl_all_sources_ucmp: getNodeUcmpResult -> resolveUcmpWeights for
+        every node and every prefix of the tracked table, on the device over
+        the resident selection. weights: {prefix: [weight per announcer name]}
+        (or a list of lists) parallel to track_select's prefixes; algo 'adj' |
+        'prefix'. Returns (weight [V, P] i64, status [V, P] u8) by node id:
+        status 0 OK, 1 no announcer reached, 2 a zero-weight announcer among the
+        min-cost ones, 3 overflow. self.ucmp_info = dict(rounds, device,
+        engine_ms) of the call. The tracked selection must be current
+        (track_select / select_delta since the last change)."""
+        lw = self._leaf_weights(weights)
+        V, P = self.num_nodes(), self._tracked_prefixes
+        weight = np.zeros((V, P), np.int64)
+        status = np.zeros((V, P), np.uint8)
+        rounds, dev, ms = C.c_uint32(), C.c_int32(), C.c_double()
+        if self._L.odl_all_sources_ucmp(self._h, UCMP_ALGOS[algo], lw.ctypes.data if lw.size else None,
+                                        lw.size, weight.ctypes.data, status.ctypes.data,
+                                        C.byref(rounds), C.byref(dev), C.byref(ms)) != 0:
+            raise LinkStateError(self._err())
+        self.ucmp_info = dict(rounds=int(rounds.value), device=bool(dev.value), engine_ms=float(ms.value))
+        return weight, status
+
+    def _ucmp_view(self, call, n: int):
+        P = self._tracked_prefixes
+        weight = np.zeros((n, P), np.int64)
+        status = np.zeros((n, P), np.uint8)
+        off = np.zeros(n * P + 1, np.uint64)
+        pw, nw = C.c_void_p(), C.c_uint64()
+        if call(weight.ctypes.data, status.ctypes.data, off.ctypes.data, C.byref(pw), C.byref(nw)) != 0:
+            raise LinkStateError(self._err())
+        try:
+            wt = (np.frombuffer(C.string_at(pw, nw.value * 8), np.int64).copy() if nw.value
+                  else np.zeros(0, np.int64))
+        finally:
+            self._L.odl_free_buf(pw)
+        return weight, status, off, wt
+
+    def ucmp_tracked(self, nodes: Sequence[str]):
+        """odl_ucmp_tracked: the per-link view of some nodes (names) from the
+        last all_sources_ucmp -> (weight [n, P], status [n, P], off [n * P + 1],
+        wt): entry (i, p)'s next-hop weights are wt[off[i * P + p] : off[i * P +
+        p + 1]], one per selected next hop in the node's distinct-neighbour
+        order (next_hop_names of select_tracked's mask), divided by their gcd."""
+        txt = "\n".join(nodes).encode()
+        return self._ucmp_view(lambda *o: self._L.odl_ucmp_tracked(self._h, txt, len(nodes), *o),
+                               len(nodes))
+
+    def ucmp_host_loop(self, weights, algo: str, nodes: Sequence[str]):
+        """odl_ucmp_host_loop: resolveUcmpWeights(getSpfResult(node), min-cost
+        announcers) per node and prefix, for some nodes -- the loop
+        all_sources_ucmp degrades to; same outputs as ucmp_tracked."""
+        lw = self._leaf_weights(weights)
+        txt = "\n".join(nodes).encode()
+        return self._ucmp_view(
+            lambda *o: self._L.odl_ucmp_host_loop(self._h, UCMP_ALGOS[algo],
+                                                  lw.ctypes.data if lw.size else None, lw.size, txt,
+                                                  len(nodes), *o), len(nodes))
+
     def next_hop_names(self, root, words, csr: Optional[Dict[str, np.ndarray]] = None,
                        names: Optional[Sequence[str]] = None) -> List[str]:
         """Names of the next hops in one (root, prefix) mask of

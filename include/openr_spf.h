@@ -477,7 +477,11 @@ int ospf_affected_roots(ospf_ctx* ctx, const uint32_t* d_dist, uint32_t n_roots,
  * event in an ECMP fabric -- gets its next-hop words re-derived where they
  * change (d_status[i] = 0: the rows now equal a fresh run's). Link changes
  * and overload toggles (node changes: the current transit bit is read) are
- * both repaired. A run whose distances would change, or beyond the repair
+ * both repaired, in one call and in either order: whether a changed link was
+ * tight before the batch is judged from its old up flag and metric alone, not
+ * from its tail's transit bit (which is the patched one), so a node that sets
+ * overload and loses or re-metrics a link in the same batch is repaired like
+ * the two events apart. A run whose distances would change, or beyond the repair
  * budget (8192 re-derivations, 1024 queued nodes), gets d_status[i] = 1 and
  * must be re-run. Digests are not maintained. Queued on `stream`. */
 int ospf_repair_runs(ospf_ctx* ctx, const uint32_t* d_roots, uint32_t n, uint32_t flags,

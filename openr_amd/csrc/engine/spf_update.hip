@@ -84,8 +84,15 @@ __global__ void affected_kernel(DevGraph g, const uint32_t* dist, uint32_t n_roo
 //     changes (was tight and is not, or became tight) re-derives v: the
 //     minimum over v's usable in-edges from reached transit nodes must still
 //     be dist(v) (else the run is flagged for a re-run), and v's next hops
-//     are pulled again (LinkState.cpp:885-901);
-//     an overload toggle of node x re-derives every tight successor of x;
+//     are pulled again (LinkState.cpp:885-901). "Was tight" is dist(u) +
+//     old metric == dist(v) on a link that was up, whatever u's transit bit:
+//     only the patched bit is known, and a u that the same batch overloads
+//     may have relayed over the link before; "became tight" and "shortens a
+//     distance" do ask for a u that relays now. (A v re-derived for a u that
+//     never relayed costs one pull that changes nothing.)
+//     an overload toggle of node x re-derives every tight successor of x
+//     over the patched row, so a link the batch also took down or raised is
+//     the LINK entry's to handle;
 //  2. a node whose next hops changed re-derives its tight successors, in
 //     increasing distance order (an LDS min-heap), so every pull reads final
 //     predecessor words.
@@ -244,12 +251,20 @@ __global__ void __launch_bounds__(256) repair_kernel(DevGraph g, RepairArgs a) {
       const uint64_t w0 = a.hop ? 1 : (dir ? c.w_ba0 : c.w_ab0);
       const uint64_t w1 = a.hop ? 1 : (dir ? c.w_ba1 : c.w_ab1);
       const uint64_t du = D[u], dv = D[v];
-      if (du == kInf || !transit(u)) continue;
-      if (c.up1 && du + w1 < dv) {  // a shorter distance
-        bail = true;
-        break;
+      if (du == kInf) continue;
+      // t0 is judged without u's transit bit: the bit read here is the
+      // patched one, and a batch may take u's link down (or raise it) and
+      // overload u at once -- u's NODE entry then walks the patched row and no
+      // longer sees v behind the link
+      const bool t0 = c.up0 && du + w0 == dv;
+      bool t1 = false;
+      if (transit(u)) {
+        if (c.up1 && du + w1 < dv) {  // a shorter distance
+          bail = true;
+          break;
+        }
+        t1 = c.up1 && du + w1 == dv;
       }
-      const bool t0 = c.up0 && du + w0 == dv, t1 = c.up1 && du + w1 == dv;
       if (t0 == t1) continue;
       const int r = rederive(v);
       if (r == 2) bail = true;

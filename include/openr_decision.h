@@ -196,6 +196,32 @@ void odl_sweep_stats(const odl_ls* ls, uint64_t* out5);
 int odl_all_sources_select(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefixes,
                            int use_link_metric, uint32_t nh_words, uint32_t* nh_words_needed,
                            uint32_t* metric, uint32_t* count, uint32_t* nh);
+/* The same under the reference's route selection (createRouteForPrefix,
+ * SpfSolver.cpp:197-458: unreached announcers dropped, the best
+ * (path preference, source preference, distance) class kept, drained
+ * announcers filtered unless all are, the route withheld below minNexthop;
+ * LinkState::allSourcesSelect with attributes -> ospf_sweep_select_policy /
+ * ospf_msweep_select_policy, or the same rule on the host path). prefixes_nl
+ * as above; attrs holds four int64 per announcer name AS WRITTEN (n_attrs of
+ * them in all, line after line, empty fields not counted): path preference,
+ * source preference (the higher wins), distance (the lower wins) and
+ * minNexthop (INT64_MIN = unset; clamped to [0, 2^32 - 1]). For a name given
+ * twice the first occurrence counts; unknown names are dropped together with
+ * their attributes. Outputs by node id, any may be NULL: metric / count / nh
+ * as above over the selected announcers, and
+ *   links     [V][n_prefixes]  next-hop links of the node's IP route;
+ *   need      [V][n_prefixes]  the largest minNexthop of the filtered class;
+ *   best      [V][n_prefixes]  bestNodeArea's node id, 0xFFFFFFFF when no
+ *                              announcer is reached;
+ *   installed [V][n_prefixes]  (bytes) 1 iff links > 0 and need <= links.
+ * nh_words / *nh_words_needed as above. Not covered: SR_MPLS per-destination
+ * next hops, KSP2 and per-area distance selection, BGP metric vectors,
+ * several areas. */
+int odl_all_sources_select_policy(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefixes,
+                                  const int64_t* attrs, uint32_t n_attrs, int use_link_metric,
+                                  uint32_t nh_words, uint32_t* nh_words_needed, uint32_t* metric,
+                                  uint32_t* count, uint32_t* nh, uint32_t* links, uint32_t* need,
+                                  uint32_t* best, uint8_t* installed);
 /* Only the selections a topology change altered (LinkState::trackSelect /
  * selectDelta / selectTracked): DecisionRouteDb::calculateUpdate
  * (SpfSolver.cpp:24-59) for odl_all_sources_select's route DB.

@@ -661,6 +661,68 @@ int ospf_sweep_select_dev(ospf_sweep* sw, const ospf_select_table* table, uint32
 /* host outputs, synchronous (after the work queued on every stream) */
 int ospf_sweep_select(ospf_sweep* sw, const ospf_select_table* table, uint32_t nh_words,
                       uint32_t* metric, uint32_t* count, uint32_t* nh);
+/* Route selection under the reference's best-route policy: what
+ * createRouteForPrefix (openr/decision/SpfSolver.cpp:197-458) decides around
+ * the minimum ospf_sweep_select takes, for every owned root and every prefix
+ * of a table, in one launch. Each announcer entry i of a prefix carries
+ *   pref[i]         the rank of its (path preference, source preference,
+ *                   distance) class within the prefix: a u32 below 2^31, the
+ *                   smaller wins (selectBestRoutes -> selectRoutes(
+ *                   SHORTEST_DISTANCE), SpfSolver.cpp:649-676, LsdbUtil.cpp:
+ *                   841-883);
+ *   min_nexthop[i]  its minNexthop threshold, 0 = unset;
+ * and its node's drained bit, which is the no-transit (overload) bit of the
+ * LOADED graph (in-place node patches are followed). Per (root r, prefix p):
+ *   R  = the entries with dist[r][a_i] != OSPF_DIST_INF (:229-244; r itself
+ *        is at distance 0 when it announces);
+ *   S  = the entries of R at the smallest pref;
+ *   S' = the undrained entries of S, or S when all of S are drained
+ *        (maybeFilterDrainedNodes, :709-731);
+ *   L  = the entries of S' at the smallest distance m.
+ * That is one unsigned minimum of key_i = pref_i << 33 | drained_i << 32 |
+ * dist_i over R (DESIGN.md §3 p'''). Outputs, in ospf_sweep_roots order:
+ *   metric [n][P]  m; OSPF_DIST_INF when R is empty;
+ *   count  [n][P]  |L|; 0 when R is empty;
+ *   nh     [n][P][nh_words]  the OR of the next-hop words of L, zero padded;
+ *   links  [n][P]  the next-hop links getNextHopsThrift emits for an IP
+ *                  route: the sum of c(r, k) over the set bits k of nh, c as
+ *                  ospf_selstate_ucmp defines it (up links r - k at the
+ *                  smallest metric r advertises on an up link to k; every up
+ *                  link under OSPF_HOP_COUNT), from the loaded graph;
+ *   need   [n][P]  the largest min_nexthop over S' (not over L: the reference
+ *                  takes it over allNodeAreas, :693-707); 0 when R is empty.
+ *                  The route is withheld iff need > links and links > 0
+ *                  (:990-1000);
+ *   best   [n][P]  bestNodeArea: r when r is in S, else the smallest node id
+ *                  of S (S, not S': picked before the drain filter, which
+ *                  never moves it, :724-728); 0xFFFFFFFF when R is empty.
+ * A root in L gets metric 0, count 1 and no next hop; a drained root that
+ * announces p beside an undrained announcer of its class is NOT selected and
+ * gets a route to the other. Any output may be NULL; every word of a wanted
+ * output is written exactly once (plain stores, no memset, no atomics).
+ * Preconditions, errors and the nothing-written-on-error rule are those of
+ * ospf_sweep_select; in addition OSPF_E_INVAL for a pref >= 2^31, a NULL pref
+ * (with announcers) and a sweep that does not describe the context's current
+ * graph (the kernel reads the live CSR and no-transit bits).
+ * Not covered: SR_MPLS per-destination next hops, K_SHORTEST_DISTANCE_2 and
+ * PER_AREA_SHORTEST_DISTANCE, BGP metric vectors, several areas, and a policy
+ * table in ospf_selstate_* (delta and UCMP over this selection). */
+typedef struct ospf_select_ptable { /* host memory */
+  uint32_t n_prefixes;
+  const uint32_t* offsets;     /* [n_prefixes + 1] */
+  const uint32_t* nodes;       /* strictly ascending per prefix */
+  const uint32_t* pref;        /* [offsets[P]], < 2^31, smaller wins */
+  const uint32_t* min_nexthop; /* [offsets[P]] or NULL (all unset) */
+} ospf_select_ptable;
+typedef struct ospf_select_pout {
+  uint32_t *metric, *count, *nh, *links, *need, *best;
+} ospf_select_pout;
+/* device outputs, queued on `stream` after the table's upload */
+int ospf_sweep_select_policy_dev(ospf_sweep* sw, const ospf_select_ptable* table,
+                                 uint32_t nh_words, const ospf_select_pout* d_out, void* stream);
+/* host outputs, synchronous (after the work queued on every stream) */
+int ospf_sweep_select_policy(ospf_sweep* sw, const ospf_select_ptable* table, uint32_t nh_words,
+                             const ospf_select_pout* out);
 /* Only the route selections a re-sweep changed: the counterpart of
  * DecisionRouteDb::calculateUpdate (openr/decision/SpfSolver.cpp:24-59, called
  * from Decision.cpp:963) for the route DB ospf_sweep_select answers. An
@@ -828,6 +890,11 @@ int ospf_msweep_digests(ospf_msweep* ms, ospf_digest* out_by_node);
  * through ospf_multi_last_error. */
 int ospf_msweep_select(ospf_msweep* ms, const ospf_select_table* table, uint32_t nh_words,
                        uint32_t* metric_by_node, uint32_t* count_by_node, uint32_t* nh_by_node);
+/* ospf_sweep_select_policy on every part for its own roots; host outputs by
+ * node id ([V][P], nh [V][P][nh_words]; any may be NULL). Nothing is written
+ * unless every part succeeded. */
+int ospf_msweep_select_policy(ospf_msweep* ms, const ospf_select_ptable* table, uint32_t nh_words,
+                              const ospf_select_pout* out_by_node);
 /* 1: this sweep's digests are gathered by RCCL, 0: by peer copies. */
 uint32_t ospf_msweep_gather_backend(const ospf_msweep* ms);
 /* The slot's sweep (row access, info) and the slot owning `root`. */
@@ -842,7 +909,9 @@ uint64_t ospf_spf_runs(const ospf_ctx* ctx);
 /* Test hook (fault injection): the after_calls-th call from now of
  * ospf_load_graph / ospf_sssp_batch / ospf_ksp2_run / ospf_sweep_create /
  * ospf_sweep_run / ospf_sweep_copy_rows / ospf_sweep_select_dev /
- * ospf_sweep_select / ospf_msweep_select (per part) / ospf_selstate_prime /
+ * ospf_sweep_select / ospf_msweep_select (per part) /
+ * ospf_sweep_select_policy_dev / ospf_sweep_select_policy /
+ * ospf_msweep_select_policy (per part) / ospf_selstate_prime /
  * ospf_selstate_update / ospf_selstate_copy / ospf_selstate_ucmp /
  * ospf_selstate_ucmp_copy on this context fails with
  * OSPF_E_DEVICE and does nothing (0 = off). Lets the caller's handling of a

@@ -41,6 +41,7 @@ ENGINE_SYMBOLS = [
     "ospf_sweep_poison",
     "ospf_sweep_row", "ospf_sweep_copy_rows", "ospf_sweep_profile", "ospf_sweep_graph_memsets",
     "ospf_sweep_select_dev", "ospf_sweep_select", "ospf_msweep_select",
+    "ospf_sweep_select_policy_dev", "ospf_sweep_select_policy", "ospf_msweep_select_policy",
     "ospf_selstate_create", "ospf_selstate_destroy", "ospf_selstate_last_error",
     "ospf_selstate_device_bytes", "ospf_selstate_prime", "ospf_selstate_update", "ospf_selstate_copy",
     "ospf_selstate_ucmp", "ospf_selstate_ucmp_copy", "ospf_selstate_ucmp_info",
@@ -57,7 +58,7 @@ DECISION_SYMBOLS = [
     "odl_ksp2_text", "odl_route_text", "odl_route_db_text", "odl_route_db_bin", "odl_free_buf", "odl_path_a_in_b", "odl_ucmp_text", "odl_csr_size", "odl_csr_export", "odl_node_name", "odl_node_id",
     "odl_apply_kvs", "odl_apply_publication", "odl_node_patches", "odl_shard_stats", "odl_route_db_multi_text", "odl_adjdbs_decode", "odl_adjdbs_stream", "odl_adjdbs_error", "odl_adjdbs_free",
     "odl_last_decode_error", "odl_get_counters", "odl_last_engine_error", "odl_inject_engine_error",
-    "odl_set_degrade", "odl_all_sources_select",
+    "odl_set_degrade", "odl_all_sources_select", "odl_all_sources_select_policy",
     "odl_track_select", "odl_select_delta", "odl_select_tracked",
     "odl_all_sources_ucmp", "odl_ucmp_tracked", "odl_ucmp_host_loop",
 ]
@@ -133,6 +134,16 @@ class ospf_sweep_launch(C.Structure):  # noqa: N801
 
 class ospf_select_table(C.Structure):  # noqa: N801
     _fields_ = [("n_prefixes", u32), ("offsets", vp), ("nodes", vp)]
+
+
+class ospf_select_ptable(C.Structure):  # noqa: N801
+    _fields_ = [("n_prefixes", u32), ("offsets", vp), ("nodes", vp), ("pref", vp),
+                ("min_nexthop", vp)]
+
+
+class ospf_select_pout(C.Structure):  # noqa: N801
+    _fields_ = [("metric", vp), ("count", vp), ("nh", vp), ("links", vp), ("need", vp),
+                ("best", vp)]
 
 
 class odl_counters(C.Structure):  # noqa: N801
@@ -219,6 +230,12 @@ def engine() -> C.CDLL:
         L.ospf_sweep_select_dev.argtypes = [vp, C.POINTER(ospf_select_table), u32, vp, vp, vp, vp]
         L.ospf_sweep_select.argtypes = [vp, C.POINTER(ospf_select_table), u32, vp, vp, vp]
         L.ospf_msweep_select.argtypes = [vp, C.POINTER(ospf_select_table), u32, vp, vp, vp]
+        L.ospf_sweep_select_policy_dev.argtypes = [vp, C.POINTER(ospf_select_ptable), u32,
+                                                   C.POINTER(ospf_select_pout), vp]
+        L.ospf_sweep_select_policy.argtypes = [vp, C.POINTER(ospf_select_ptable), u32,
+                                               C.POINTER(ospf_select_pout)]
+        L.ospf_msweep_select_policy.argtypes = [vp, C.POINTER(ospf_select_ptable), u32,
+                                                C.POINTER(ospf_select_pout)]
         L.ospf_selstate_create.argtypes = [vp, C.POINTER(ospf_select_table), C.POINTER(vp)]
         L.ospf_selstate_destroy.argtypes = [vp]
         L.ospf_selstate_last_error.argtypes = [vp]
@@ -268,6 +285,8 @@ def decision() -> C.CDLL:
         L.odl_all_sources_prefetch.argtypes = [vp, i32]
         L.odl_all_sources_digests.argtypes = [vp, i32, vp]
         L.odl_all_sources_select.argtypes = [vp, cp, u32, i32, u32, C.POINTER(u32), vp, vp, vp]
+        L.odl_all_sources_select_policy.argtypes = [vp, cp, u32, vp, u32, i32, u32,
+                                                    C.POINTER(u32), vp, vp, vp, vp, vp, vp, vp]
         L.odl_track_select.argtypes = [vp, cp, u32, i32]
         L.odl_select_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
                                        C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]

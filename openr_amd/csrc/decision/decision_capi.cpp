@@ -432,6 +432,57 @@ int odl_all_sources_select(odl_ls* h, const char* prefixes_nl, uint32_t n_prefix
   }, -1);
 }
 
+int odl_all_sources_select_policy(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes,
+                                  const int64_t* attrs, uint32_t n_attrs, int use_link_metric,
+                                  uint32_t nh_words, uint32_t* nh_words_needed, uint32_t* metric,
+                                  uint32_t* count, uint32_t* nh, uint32_t* links, uint32_t* need,
+                                  uint32_t* best, uint8_t* installed) {
+  return guard(h, [&]() -> int {
+    const uint32_t words = h->ls.selectWords();
+    if (nh_words_needed) *nh_words_needed = words;
+    if (!nh_words) return 0;  // the width only
+    if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
+    if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
+    std::vector<std::vector<std::string>> prefixes;
+    std::vector<std::vector<odl::LinkState::SelectAttr>> at;
+    prefixes.reserve(n_prefixes);
+    at.reserve(n_prefixes);
+    size_t used = 0;
+    for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
+      std::vector<std::string> names;
+      std::vector<odl::LinkState::SelectAttr> as;
+      for (size_t b = 0; b < ln.size();) {  // tab-separated, empty fields skipped
+        size_t e = ln.find('\t', b);
+        if (e == std::string::npos) e = ln.size();
+        if (e > b) {
+          if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than announcer names");
+          const int64_t* a = attrs + 4 * used++;
+          odl::LinkState::SelectAttr sa;
+          sa.pathPreference = a[0];
+          sa.sourcePreference = a[1];
+          sa.distance = a[2];
+          if (a[3] != std::numeric_limits<int64_t>::min()) sa.minNexthop = a[3];
+          names.emplace_back(ln, b, e - b);
+          as.push_back(sa);
+        }
+        b = e + 1;
+      }
+      prefixes.push_back(std::move(names));
+      at.push_back(std::move(as));
+    }
+    if (used != n_attrs) throw std::invalid_argument("more attribute sets than announcer names");
+    const auto r = h->ls.allSourcesSelect(prefixes, at, use_link_metric != 0, nh_words);
+    if (metric) std::copy(r.metric.begin(), r.metric.end(), metric);
+    if (count) std::copy(r.count.begin(), r.count.end(), count);
+    if (nh) std::copy(r.nh.begin(), r.nh.end(), nh);
+    if (links) std::copy(r.links.begin(), r.links.end(), links);
+    if (need) std::copy(r.need.begin(), r.need.end(), need);
+    if (best) std::copy(r.best.begin(), r.best.end(), best);
+    if (installed) std::copy(r.installed.begin(), r.installed.end(), installed);
+    return 0;
+  }, -1);
+}
+
 int odl_track_select(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes, int use_link_metric) {
   return guard(h, [&]() -> int {
     h->ls.trackSelect(prefixLines(prefixes_nl, n_prefixes), use_link_metric != 0);

@@ -1227,6 +1227,194 @@ LinkState::SelectResult LinkState::allSourcesSelectImpl(
   return out;
 }
 
+// ---------------------------------------------------------------- select policy
+LinkState::PolicyResult LinkState::allSourcesSelect(
+    const std::vector<std::vector<std::string>>& prefixes,
+    const std::vector<std::vector<SelectAttr>>& attrs, bool useLinkMetric, uint32_t nhWords) {
+  snapshot();
+  if (attrs.size() != prefixes.size())
+    throw std::invalid_argument("allSourcesSelect: one attribute list per prefix");
+  const uint32_t need = selectWords();
+  if (nhWords && nhWords < need)
+    throw std::invalid_argument("allSourcesSelect: nhWords " + std::to_string(nhWords) +
+                                " below the widest node's " + std::to_string(need));
+  const size_t P = prefixes.size();
+  std::vector<std::vector<uint32_t>> ann(P), pref(P), mnh(P);
+  for (size_t p = 0; p < P; ++p) {
+    if (attrs[p].size() != prefixes[p].size())
+      throw std::invalid_argument("allSourcesSelect: one attribute set per announcer");
+    // names -> ids: unknown names dropped with their attributes, the first
+    // occurrence of a name counts; ascending by id
+    std::vector<std::pair<uint32_t, size_t>> ent;  // (id, position in the prefix's list)
+    for (size_t i = 0; i < prefixes[p].size(); ++i) {
+      const auto it = csr_->ids.find(prefixes[p][i]);
+      if (it != csr_->ids.end()) ent.emplace_back(it->second, i);
+    }
+    std::sort(ent.begin(), ent.end());
+    ent.erase(std::unique(ent.begin(), ent.end(),
+                          [](const auto& a, const auto& b) { return a.first == b.first; }),
+              ent.end());
+    // the dense class rank: (pathPreference, sourcePreference) descending,
+    // distance ascending (selectRoutes(SHORTEST_DISTANCE), LsdbUtil.cpp:841-883)
+    using Cls = std::array<int64_t, 3>;
+    auto cls = [&](size_t i) {
+      const SelectAttr& a = attrs[p][i];
+      return Cls{a.pathPreference, a.sourcePreference, a.distance};
+    };
+    auto better = [](const Cls& a, const Cls& b) {
+      if (a[0] != b[0]) return a[0] > b[0];
+      if (a[1] != b[1]) return a[1] > b[1];
+      return a[2] < b[2];
+    };
+    std::vector<Cls> classes;
+    for (const auto& e : ent) classes.push_back(cls(e.second));
+    std::sort(classes.begin(), classes.end(), better);
+    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+    for (const auto& e : ent) {
+      ann[p].push_back(e.first);
+      pref[p].push_back((uint32_t)(std::lower_bound(classes.begin(), classes.end(), cls(e.second), better) -
+                                   classes.begin()));
+      const auto& mn = attrs[p][e.second].minNexthop;
+      const int64_t v = mn ? std::clamp<int64_t>(*mn, 0, 0xFFFFFFFFll) : 0;
+      mnh[p].push_back((uint32_t)v);
+    }
+  }
+  const uint32_t W = nhWords ? nhWords : need;
+  return guarded([&] { return allSourcesPolicyImpl(ann, pref, mnh, useLinkMetric, W); });
+}
+
+LinkState::PolicyResult LinkState::allSourcesPolicyImpl(
+    const std::vector<std::vector<uint32_t>>& ann, const std::vector<std::vector<uint32_t>>& pref,
+    const std::vector<std::vector<uint32_t>>& mnh, bool useLinkMetric, uint32_t W) {
+  snapshot();
+  const size_t V = csr_->names.size(), P = ann.size();
+  PolicyResult out;
+  out.prefixes = (uint32_t)P;
+  out.words = W;
+  out.metric.assign(V * P, kInf);
+  out.count.assign(V * P, 0);
+  out.links.assign(V * P, 0);
+  out.need.assign(V * P, 0);
+  out.best.assign(V * P, kInf);
+  out.nh.assign(V * P * W, 0);
+  out.installed.assign(V * P, 0);
+  if (!V || !P) return out;
+  auto install = [&] {
+    for (size_t i = 0; i < V * P; ++i)
+      out.installed[i] = out.links[i] > 0 && out.need[i] <= out.links[i];
+  };
+  if (hostRun(useLinkMetric)) {
+    // createRouteForPrefix's steps (SpfSolver.cpp:229-244, 649-676, 709-731,
+    // 990-1000) over getSpfResult of every node
+    std::vector<uint32_t> nbrs, minw, c;
+    for (uint32_t r = 0; r < V; ++r) {
+      const SpfResult& res = getSpfResult(csr_->names[r], useLinkMetric);
+      // distinct neighbours, ascending (the bit order), and the links r - k
+      // getNextHopsThrift emits: up, at the smallest metric r advertises
+      // towards k (every up link under hop count)
+      nbrs.clear();
+      for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e)
+        if (csr_->col[e] != r && (nbrs.empty() || nbrs.back() != csr_->col[e]))
+          nbrs.push_back(csr_->col[e]);
+      minw.assign(nbrs.size(), kInf);
+      c.assign(nbrs.size(), 0);
+      auto slot = [&](uint32_t id) {
+        return (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), id) - nbrs.begin());
+      };
+      for (int pass = 0; pass < 2; ++pass)
+        for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e) {
+          if (csr_->col[e] == r || !csr_->edgeUp[e]) continue;
+          const uint32_t k = slot(csr_->col[e]);
+          if (!pass) minw[k] = std::min(minw[k], csr_->metric[e]);
+          else if (!useLinkMetric || csr_->metric[e] == minw[k]) ++c[k];
+        }
+      for (size_t p = 0; p < P; ++p) {
+        const size_t n = ann[p].size();
+        // reached announcers, then the best class among them
+        std::vector<size_t> R;
+        std::vector<Metric> d(n, 0);
+        for (size_t i = 0; i < n; ++i) {
+          const auto it = res.find(csr_->names[ann[p][i]]);
+          if (it == res.end()) continue;
+          d[i] = it->second.metric();
+          R.push_back(i);
+        }
+        if (R.empty()) continue;
+        uint32_t top = kInf;
+        for (size_t i : R) top = std::min(top, pref[p][i]);
+        std::vector<size_t> S, Sf;
+        for (size_t i : R)
+          if (pref[p][i] == top) S.push_back(i);
+        for (size_t i : S)
+          if (!csr_->noTransit[ann[p][i]]) Sf.push_back(i);
+        if (Sf.empty()) Sf = S;
+        Metric shortest = std::numeric_limits<Metric>::max();
+        for (size_t i : Sf) shortest = std::min(shortest, d[i]);
+        const size_t cell = r * P + p;
+        uint32_t* words = out.nh.data() + cell * W;
+        for (size_t i : Sf) {
+          out.need[cell] = std::max(out.need[cell], mnh[p][i]);
+          if (d[i] != shortest) continue;
+          ++out.count[cell];
+          for (const auto& nhName : res.at(csr_->names[ann[p][i]]).nextHops()) {
+            const uint32_t k = slot(csr_->ids.at(nhName));
+            if (k < nbrs.size() && nbrs[k] == csr_->ids.at(nhName) && k / 32 < W)
+              words[k / 32] |= 1u << (k % 32);
+          }
+        }
+        out.metric[cell] = (uint32_t)shortest;
+        out.best[cell] = ann[p][S.front()];  // ascending ids: the smallest of S
+        for (size_t i : S)
+          if (ann[p][i] == r) out.best[cell] = r;
+        for (uint32_t k = 0; k < nbrs.size() && k / 32 < W; ++k)
+          if (words[k / 32] >> (k % 32) & 1u) out.links[cell] += c[k];
+      }
+    }
+    install();
+    return out;
+  }
+  prefetchAllSources(useLinkMetric);
+  std::vector<uint32_t> off(P + 1, 0), nodes, prefs, mins;
+  for (size_t p = 0; p < P; ++p) {
+    nodes.insert(nodes.end(), ann[p].begin(), ann[p].end());
+    prefs.insert(prefs.end(), pref[p].begin(), pref[p].end());
+    mins.insert(mins.end(), mnh[p].begin(), mnh[p].end());
+    off[p + 1] = (uint32_t)nodes.size();
+  }
+  const ospf_select_ptable t{(uint32_t)P, off.data(), nodes.data(), prefs.data(), mins.data()};
+  if (msweep_) {
+    const ospf_select_pout o{out.metric.data(), out.count.data(), out.nh.data(),
+                             out.links.data(),  out.need.data(),  out.best.data()};
+    const int rc = ospf_msweep_select_policy(msweep_, &t, W, &o);
+    if (rc != OSPF_OK) throw EngineError(rc, ospf_multi_last_error(multi_));
+    install();
+    return out;
+  }
+  ospf_sweep_info info{};
+  ospf_sweep_get_info(sweep_, &info);
+  std::vector<uint32_t> roots(info.n_roots);
+  ospf_sweep_roots(sweep_, roots.data());
+  const size_t n = roots.size();
+  std::vector<uint32_t> m(n * P), k(n * P), nh(n * P * W), li(n * P), ne(n * P), be(n * P);
+  const ospf_select_pout o{m.data(), k.data(), nh.data(), li.data(), ne.data(), be.data()};
+  const int rc = ospf_sweep_select_policy(sweep_, &t, W, &o);
+  if (rc != OSPF_OK) throw EngineError(rc, ospf_sweep_last_error(sweep_));
+  for (size_t i = 0; i < n; ++i) {  // owned-roots order -> node id
+    const size_t r = roots[i];
+    auto put = [&](const std::vector<uint32_t>& src, std::vector<uint32_t>& dst, size_t per) {
+      std::copy(src.begin() + i * per, src.begin() + (i + 1) * per, dst.begin() + r * per);
+    };
+    put(m, out.metric, P);
+    put(k, out.count, P);
+    put(nh, out.nh, P * W);
+    put(li, out.links, P);
+    put(ne, out.need, P);
+    put(be, out.best, P);
+  }
+  install();
+  return out;
+}
+
 // ---------------------------------------------------------------- trackSelect
 std::vector<std::vector<uint32_t>> LinkState::trackAnn() const {
   // names -> ids as allSourcesSelect: unknown names dropped, ascending, distinct

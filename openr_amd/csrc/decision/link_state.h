@@ -555,6 +555,36 @@ class LinkState {
   };
   SelectResult allSourcesSelect(const std::vector<std::vector<std::string>>& prefixes,
                                 bool useLinkMetric = true, uint32_t nhWords = 0);
+  // The same under the reference's route selection (createRouteForPrefix,
+  // SpfSolver.cpp:197-458; prefixRoute restates it per node): `attrs` holds,
+  // parallel to `prefixes`, the announcers' odl::PrefixEntry fields that
+  // selection reads. Per node and prefix: the unreached announcers dropped,
+  // the best (pathPreference, sourcePreference descending, distance
+  // ascending) class kept, its drained (overloaded) members filtered unless
+  // all are, then the minimum taken (ospf_sweep_select_policy /
+  // ospf_msweep_select_policy: the class ranks are computed here, minNexthop
+  // clamped to [0, 2^32 - 1] -- prefixRoute compares signed, so a negative
+  // threshold never withholds). Beside metric / count / nh: links = the
+  // next-hop links of an IP route, need = the largest minNexthop of the
+  // filtered class, best = bestNodeArea's node id (kInf: none reached) and
+  // installed = 1 iff links > 0 and need <= links. For a name given twice the
+  // first occurrence counts; unknown names are dropped with their attributes.
+  // On the host path the same rule runs over getSpfResult of every node.
+  // Not covered: SR_MPLS per-destination next hops, KSP2 / per-area distance
+  // selection, BGP metric vectors, several areas.
+  struct SelectAttr {
+    int64_t pathPreference = 0, sourcePreference = 0, distance = 0;
+    std::optional<int64_t> minNexthop;
+  };
+  struct PolicyResult {
+    uint32_t prefixes = 0, words = 0;
+    std::vector<uint32_t> metric, count, links, need, best;  // [V][prefixes]
+    std::vector<uint32_t> nh;                                 // [V][prefixes][words]
+    std::vector<uint8_t> installed;                           // [V][prefixes]
+  };
+  PolicyResult allSourcesSelect(const std::vector<std::vector<std::string>>& prefixes,
+                                const std::vector<std::vector<SelectAttr>>& attrs,
+                                bool useLinkMetric = true, uint32_t nhWords = 0);
   // next-hop words of the widest node of the snapshot
   uint32_t selectWords();
   // Only the selections a topology change altered: the counterpart of
@@ -846,6 +876,11 @@ class LinkState {
   void prefetchAllSourcesImpl(bool useLinkMetric);
   std::vector<ospf_digest> allSourcesDigestsImpl(bool useLinkMetric);
   SelectResult allSourcesSelectImpl(const std::vector<std::vector<uint32_t>>& ann,
+                                    bool useLinkMetric, uint32_t W);
+  // pref: the class rank, mnh: the clamped threshold, parallel to ann
+  PolicyResult allSourcesPolicyImpl(const std::vector<std::vector<uint32_t>>& ann,
+                                    const std::vector<std::vector<uint32_t>>& pref,
+                                    const std::vector<std::vector<uint32_t>>& mnh,
                                     bool useLinkMetric, uint32_t W);
   // ---- trackSelect ----
   bool tracking_ = false, trackMetric_ = true;

@@ -376,6 +376,69 @@ int ospf_msweep_select(ospf_msweep* ms, const ospf_select_table* t, uint32_t nh_
   return OSPF_OK;
 }
 
+int ospf_msweep_select_policy(ospf_msweep* ms, const ospf_select_ptable* t, uint32_t nh_words,
+                              const ospf_select_pout* out) {
+  if (!ms || !t || !out) return OSPF_E_INVAL;
+  const size_t n = ms->parts.size(), P = t->n_prefixes;
+  auto part_fail = [&](size_t i, int rc) {
+    ms->m->err = ms->parts[i]->err;
+    return rc;
+  };
+  auto dev_fail = [&](const char* what) {
+    (void)hipGetLastError();
+    ms->m->err = std::string("msweep select policy: ") + what;
+    return OSPF_E_DEVICE;
+  };
+  // every part queues its own roots' select on its device, then the copies
+  std::vector<PolicyOut> d(n);
+  for (size_t i = 0; i < n; ++i) {
+    ospf_sweep* s = ms->parts[i];
+    if (ospf_int::injected(s->c)) return part_fail(i, sfail(s, OSPF_E_DEVICE, s->c->err));
+    const size_t cells = s->roots.size() * P;
+    if (cells && s->ran) {
+      if (hipSetDevice(s->c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return dev_fail("hipDeviceSynchronize");
+      if (!d[i].alloc(cells, std::max(1u, nh_words), out)) {
+        (void)hipGetLastError();
+        ms->m->err = "msweep select policy: hipMalloc of the outputs";
+        return OSPF_E_NOMEM;
+      }
+    }
+    const int rc = policy_queue(s, t, nh_words, &d[i].o, nullptr);
+    if (rc) return part_fail(i, rc);
+  }
+  // the parts' outputs (owned-roots order) into host buffers of this call
+  // first: a failed copy leaves the caller's as they were
+  std::vector<std::vector<uint32_t>> tmp(n * 6);
+  for (size_t i = 0; i < n; ++i) {
+    ospf_sweep* s = ms->parts[i];
+    const size_t cells = s->roots.size() * P;
+    if (!cells) continue;
+    if (hipSetDevice(s->c->device) != hipSuccess) return dev_fail("hipSetDevice");
+    uint32_t* const src[6] = {d[i].o.metric, d[i].o.count, d[i].o.nh,
+                              d[i].o.links,  d[i].o.need,  d[i].o.best};
+    for (int k = 0; k < 6; ++k) {
+      if (!src[k]) continue;
+      auto& h = tmp[i * 6 + k];
+      h.resize(cells * (k == 2 ? nh_words : 1u));
+      if (hipMemcpy(h.data(), src[k], h.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return dev_fail("hipMemcpy");
+    }
+  }
+  uint32_t* const dst[6] = {out->metric, out->count, out->nh, out->links, out->need, out->best};
+  for (size_t i = 0; i < n; ++i) {
+    ospf_sweep* s = ms->parts[i];
+    for (int k = 0; k < 6; ++k) {
+      const auto& h = tmp[i * 6 + k];
+      if (h.empty()) continue;
+      const size_t per = P * (k == 2 ? nh_words : 1u);
+      for (size_t j = 0; j < s->roots.size(); ++j)  // owned-roots order -> node id
+        std::copy(h.begin() + j * per, h.begin() + (j + 1) * per, dst[k] + (size_t)s->roots[j] * per);
+    }
+  }
+  return OSPF_OK;
+}
+
 ospf_sweep* ospf_msweep_part(ospf_msweep* ms, uint32_t slot) {
   return (ms && slot < ms->parts.size()) ? ms->parts[slot] : nullptr;
 }

@@ -306,6 +306,15 @@ void release(ospf_sweep* s) {
   s->d_sel_tab = nullptr;
   s->d_sel_rows = nullptr;  // one of allocs
   s->sel_tab_words = 0;
+  if (s->pol_ev) {
+    hipEventSynchronize(s->pol_ev);
+    hipEventDestroy(s->pol_ev);
+  }
+  if (s->d_pol_tab) hipFree(s->d_pol_tab);
+  s->pol_ev = nullptr;
+  s->d_pol_tab = nullptr;
+  s->d_pol_roots = nullptr;  // one of allocs
+  s->pol_tab_words = 0;
   for (hipStream_t st : s->streams) {
     if (!st) continue;
     if (s->c) {

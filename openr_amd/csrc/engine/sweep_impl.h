@@ -72,6 +72,14 @@ struct ospf_sweep {
   uint32_t* d_sel_tab = nullptr;
   size_t sel_tab_words = 0;
   hipEvent_t sel_ev = nullptr;
+  // ospf_sweep_select_policy*: the owned roots' node ids on the device
+  // (uploaded on first use), the last policy table's device copy (offsets,
+  // nodes, pref, min_nexthop; grown on demand) and the event after the last
+  // launch that reads it
+  uint32_t* d_pol_roots = nullptr;
+  uint32_t* d_pol_tab = nullptr;
+  size_t pol_tab_words = 0;
+  hipEvent_t pol_ev = nullptr;
 };
 
 namespace ospf_int {
@@ -264,6 +272,28 @@ struct SelectOut {
     return (!wm || hipMalloc((void**)&m, cells * 4) == hipSuccess) &&
            (!wk || hipMalloc((void**)&k, cells * 4) == hipSuccess) &&
            (!wnh || hipMalloc((void**)&nh, cells * W * 4) == hipSuccess);
+  }
+};
+
+// ---------------------------------------------------------------- select policy
+// ospf_sweep_select_policy_dev without the fault-injection hook (the host and
+// multi-device calls hook once themselves)
+int policy_queue(ospf_sweep* s, const ospf_select_ptable* t, uint32_t nh_words,
+                 const ospf_select_pout* d_out, void* stream);
+
+// device outputs of one policy select (only the wanted ones of `want`), freed
+// by the destructor
+struct PolicyOut {
+  ospf_select_pout o{};
+  ~PolicyOut() {
+    for (uint32_t* p : {o.metric, o.count, o.nh, o.links, o.need, o.best})
+      if (p) (void)hipFree(p);
+  }
+  bool alloc(size_t cells, uint32_t W, const ospf_select_pout* want) {
+    auto get = [](uint32_t** p, size_t words) { return hipMalloc((void**)p, words * 4) == hipSuccess; };
+    return (!want->metric || get(&o.metric, cells)) && (!want->count || get(&o.count, cells)) &&
+           (!want->nh || get(&o.nh, cells * W)) && (!want->links || get(&o.links, cells)) &&
+           (!want->need || get(&o.need, cells)) && (!want->best || get(&o.best, cells));
   }
 };
 

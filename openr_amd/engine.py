@@ -42,6 +42,37 @@ def select_table(offsets: Sequence[int], nodes: Sequence[int]):
     return t, (off, ids)
 
 
+POLICY_OUTPUTS = ("metric", "count", "nh", "links", "need", "best")
+
+
+def select_ptable(offsets: Sequence[int], nodes: Sequence[int], pref: Optional[Sequence[int]],
+                  min_nexthop: Optional[Sequence[int]] = None):
+    """(ospf_select_ptable, the arrays it points into): the CSR prefix table
+    with a class rank (< 2^31, smaller wins) and optionally a minNexthop
+    threshold (0 = unset) per announcer entry. pref None passes NULL."""
+    off = np.ascontiguousarray(offsets, np.uint32)
+    ids = np.ascontiguousarray(nodes, np.uint32)
+    if off.size < 1:
+        raise ValueError("offsets needs n_prefixes + 1 entries")
+    pr = None if pref is None else np.ascontiguousarray(pref, np.uint32)
+    mn = None if min_nexthop is None else np.ascontiguousarray(min_nexthop, np.uint32)
+    for a in (pr, mn):
+        if a is not None and a.size != ids.size:
+            raise ValueError("pref / min_nexthop: one per announcer entry")
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    t = N.ospf_select_ptable(int(off.size - 1), off.ctypes.data, ptr(ids), ptr(pr), ptr(mn))
+    return t, (off, ids, pr, mn)
+
+
+def _policy_host_out(n: int, P: int, W: int, want: Sequence[str]):
+    bad = set(want) - set(POLICY_OUTPUTS)
+    if bad:
+        raise ValueError(f"unknown outputs {sorted(bad)}")
+    arrs = {k: np.zeros((n, P, W) if k == "nh" else (n, P), np.uint32) for k in want}
+    o = N.ospf_select_pout(*[arrs[k].ctypes.data if k in arrs else None for k in POLICY_OUTPUTS])
+    return o, arrs
+
+
 # ospf_select_change / odl_select_change records
 CHANGE_DTYPE = np.dtype([("root", np.uint32), ("prefix", np.uint32), ("metric", np.uint32),
                          ("count", np.uint32)])
@@ -429,6 +460,34 @@ class Sweep:
         self._check(self._L.ospf_sweep_select_dev(self._h, C.byref(t), nh_words, d_metric or None,
                                                   d_count or None, d_nh or None, stream or None))
 
+    def select_policy(self, offsets: Sequence[int], nodes: Sequence[int],
+                      pref: Optional[Sequence[int]],
+                      min_nexthop: Optional[Sequence[int]] = None, nh_words: int = 0,
+                      want: Sequence[str] = POLICY_OUTPUTS) -> Dict[str, np.ndarray]:
+        """ospf_sweep_select_policy: the reference's best-route selection
+        (reached announcers, best pref class, drain filter, minNexthop) for
+        every owned root and every prefix -> {metric, count, links, need, best
+        [n, P] u32, nh [n, P, W] u32} in `roots` order; only the outputs named
+        in `want` are computed."""
+        t, keep = select_ptable(offsets, nodes, pref, min_nexthop)
+        W = nh_words or max(1, self.max_nh_words)
+        o, arrs = _policy_host_out(self.n_roots, int(t.n_prefixes), W, want)
+        self._check(self._L.ospf_sweep_select_policy(self._h, C.byref(t), W, C.byref(o)))
+        return arrs
+
+    def select_policy_dev(self, offsets: Sequence[int], nodes: Sequence[int],
+                          pref: Optional[Sequence[int]],
+                          min_nexthop: Optional[Sequence[int]], nh_words: int, *,
+                          d_metric: int = 0, d_count: int = 0, d_nh: int = 0, d_links: int = 0,
+                          d_need: int = 0, d_best: int = 0, stream: int = 0) -> None:
+        """ospf_sweep_select_policy_dev: the same into device memory (raw
+        pointers; 0 = not wanted), queued on `stream` after the table's upload."""
+        t, keep = select_ptable(offsets, nodes, pref, min_nexthop)
+        o = N.ospf_select_pout(d_metric or None, d_count or None, d_nh or None, d_links or None,
+                               d_need or None, d_best or None)
+        self._check(self._L.ospf_sweep_select_policy_dev(self._h, C.byref(t), nh_words,
+                                                         C.byref(o), stream or None))
+
     def profile(self, reps: int = 3):
         """Every launch unit timed alone on its stream -> list of dicts."""
         cap = max(1, self.n_launches)
@@ -683,6 +742,23 @@ class MultiSweep:
                                                      metric.ctypes.data, count.ctypes.data,
                                                      nh.ctypes.data))
         return metric, count, nh
+
+    def select_policy(self, offsets: Sequence[int], nodes: Sequence[int],
+                      pref: Optional[Sequence[int]],
+                      min_nexthop: Optional[Sequence[int]] = None, nh_words: int = 0,
+                      want: Sequence[str] = POLICY_OUTPUTS) -> Dict[str, np.ndarray]:
+        """ospf_msweep_select_policy: Sweep.select_policy on every part for its
+        own roots -> the same arrays by node id ([V, P], nh [V, P, W])."""
+        t, keep = select_ptable(offsets, nodes, pref, min_nexthop)
+        if not nh_words:
+            gi = N.ospf_sweep_info()
+            for slot in range(self.multi.n):
+                self._L.ospf_sweep_get_info(self._L.ospf_msweep_part(self._h, slot), C.byref(gi))
+                nh_words = max(nh_words, int(gi.max_nh_words), 1)
+        o, arrs = _policy_host_out(self.multi.V, int(t.n_prefixes), nh_words, want)
+        self.multi._check(self._L.ospf_msweep_select_policy(self._h, C.byref(t), nh_words,
+                                                            C.byref(o)))
+        return arrs
 
     @property
     def gather_backend(self) -> str:

@@ -564,6 +564,46 @@ class LinkState:
             raise LinkStateError(self._err())
         return metric, count, nh
 
+    def all_sources_select_policy(self, prefixes: Dict[str, Sequence[tuple]],
+                                  use_link_metric: bool = True, nh_words: int = 0) -> dict:
+        """The reference's route selection for every node and every prefix
+        (odl_all_sources_select_policy; createRouteForPrefix, SpfSolver.cpp:
+        197-458): unreached announcers dropped, the best (path preference,
+        source preference, distance) class kept, drained announcers filtered
+        unless all are, then the minimum. prefixes: {prefix: [(name,
+        path_pref, source_pref, distance, min_nexthop_or_None), ...]}; for a
+        name given twice the first counts, unknown names are dropped. Returns
+        a dict by node id (node_names() order), columns in the dict's order:
+        metric / count / links / need / best [V, P] u32, nh [V, P, W] u32 and
+        installed [V, P] bool (links > 0 and need <= links)."""
+        unset = -(1 << 63)
+        lines, attrs = [], []
+        for ann in prefixes.values():
+            for nm, pp, sp, dist, mn in ann:
+                if not nm or "\n" in nm or "\t" in nm:
+                    raise ValueError("node names must be non-empty, without tabs and newlines")
+                attrs.append((int(pp), int(sp), int(dist), unset if mn is None else int(mn)))
+            lines.append("\t".join(a[0] for a in ann))
+        txt = "\n".join(lines).encode()
+        at = np.ascontiguousarray(attrs, np.int64).reshape(-1, 4)
+        args = (self._h, txt, len(lines), at.ctypes.data if at.size else None, at.shape[0],
+                int(use_link_metric))
+        need = C.c_uint32(0)
+        if self._L.odl_all_sources_select_policy(*args, 0, C.byref(need), None, None, None, None,
+                                                 None, None, None) != 0:
+            raise LinkStateError(self._err())
+        V, P, W = self.num_nodes(), len(lines), nh_words or int(need.value)
+        out = {k: np.zeros((V, P), np.uint32) for k in ("metric", "count", "links", "need", "best")}
+        out["nh"] = np.zeros((V, P, W), np.uint32)
+        inst = np.zeros((V, P), np.uint8)
+        if self._L.odl_all_sources_select_policy(
+                *args, W, None, out["metric"].ctypes.data, out["count"].ctypes.data,
+                out["nh"].ctypes.data, out["links"].ctypes.data, out["need"].ctypes.data,
+                out["best"].ctypes.data, inst.ctypes.data) != 0:
+            raise LinkStateError(self._err())
+        out["installed"] = inst.astype(bool)
+        return out
+
     @staticmethod
     def _prefix_lines(prefixes: Dict[str, Sequence[str]]) -> List[str]:
         lines = ["\t".join(a) for a in prefixes.values()]

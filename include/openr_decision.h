@@ -255,6 +255,35 @@ int odl_select_delta(odl_ls* ls, uint32_t* n_changes, uint32_t* n_rebased, uint3
                      int* full, void** changes, void** nh, void** rebased);
 int odl_select_tracked(odl_ls* ls, const char* nodes_nl, uint32_t n, uint32_t nh_words,
                        uint32_t* metric, uint32_t* count, uint32_t* nh);
+/* The same over the policy selection of odl_all_sources_select_policy
+ * (LinkState::trackSelect with attributes / policyDelta / policyTracked /
+ * setTrackedAttrs): what calculateUpdate diffs when best-route selection, a
+ * drained node or minNexthop are in play. odl_track_select_policy takes the
+ * prefix lines and attributes as odl_all_sources_select_policy does and stores
+ * the policy selection as the baseline (on the device:
+ * ospf_selstate_create_policy). odl_policy_delta is odl_select_delta with
+ * odl_policy_change records: an entry changed when any of metric, count,
+ * links, need, best or a next-hop word differs; installed = links > 0 && need
+ * <= links. odl_policy_tracked copies the baseline of n nodes in
+ * odl_all_sources_select_policy's layout (any output may be NULL).
+ * odl_set_tracked_attrs replaces the attributes (n_attrs sets, parallel to the
+ * tracked lines' names): nothing stored changes; the next odl_policy_delta
+ * reports what the new attributes changed, with or without a topology event.
+ * A table tracked with attributes refuses odl_select_delta /
+ * odl_select_tracked, one tracked without refuses these calls (-1).
+ * odl_all_sources_ucmp / odl_ucmp_tracked / odl_ucmp_host_loop on such a table
+ * run over the policy selection. Host path and degraded behaviour as above. */
+typedef struct odl_policy_change {
+  uint32_t node, prefix, metric, count, links, need, best, installed;
+} odl_policy_change;
+int odl_track_select_policy(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefixes,
+                            const int64_t* attrs, uint32_t n_attrs, int use_link_metric);
+int odl_policy_delta(odl_ls* ls, uint32_t* n_changes, uint32_t* n_rebased, uint32_t* nh_words,
+                     int* full, void** changes, void** nh, void** rebased);
+int odl_policy_tracked(odl_ls* ls, const char* nodes_nl, uint32_t n, uint32_t nh_words,
+                       uint32_t* metric, uint32_t* count, uint32_t* nh, uint32_t* links,
+                       uint32_t* need, uint32_t* best, uint8_t* installed);
+int odl_set_tracked_attrs(odl_ls* ls, const int64_t* attrs, uint32_t n_attrs);
 /* UCMP weights of every node for every prefix of the tracked table
  * (LinkState::allSourcesUcmp): SpfSolver::getNodeUcmpResult ->
  * resolveUcmpWeights (SpfSolver.cpp:1091-1161, LinkState.cpp:913-1033) for all

@@ -705,8 +705,9 @@ int ospf_sweep_select(ospf_sweep* sw, const ospf_select_table* table, uint32_t n
  * (with announcers) and a sweep that does not describe the context's current
  * graph (the kernel reads the live CSR and no-transit bits).
  * Not covered: SR_MPLS per-destination next hops, K_SHORTEST_DISTANCE_2 and
- * PER_AREA_SHORTEST_DISTANCE, BGP metric vectors, several areas, and a policy
- * table in ospf_selstate_* (delta and UCMP over this selection). */
+ * PER_AREA_SHORTEST_DISTANCE, BGP metric vectors, several areas. (The same
+ * selection kept resident, its delta and UCMP over it: the policy state of
+ * ospf_selstate_create_policy below.) */
 typedef struct ospf_select_ptable { /* host memory */
   uint32_t n_prefixes;
   const uint32_t* offsets;     /* [n_prefixes + 1] */
@@ -841,6 +842,60 @@ int ospf_selstate_ucmp_copy(ospf_selstate* st, const uint32_t* roots, uint32_t n
 /* rounds of the last run (0: none yet) and the graph's distinct-neighbour
  * slots (the length of link_weight_sum); either may be NULL */
 int ospf_selstate_ucmp_info(const ospf_selstate* st, uint32_t* rounds, uint32_t* n_slots);
+/* A select state that holds ospf_sweep_select_policy's selection: what
+ * calculateUpdate diffs and getNodeUcmpResult walks from when best-route
+ * selection, drained nodes or minNexthop are in play (the reference applies
+ * the policy before both).
+ *   create_policy  the table and its pref / min_nexthop columns are copied;
+ *                  the table's contract and errors are ospf_sweep_select_policy's
+ *                  (a pref >= 2^31, a NULL pref with announcers: OSPF_E_INVAL).
+ *                  A policy state keeps, per root and by node id, metric [P],
+ *                  count [P], links [P], need [P], best [P], nh [P][W_root]
+ *                  (SoA, no padding), twice: two buffers of the sum over the
+ *                  roots of P * (5 + W_root) * 4 bytes.
+ *   prime          ospf_selstate_prime, unchanged.
+ *   update_policy  ospf_selstate_update for this state: an entry changed when
+ *                  any of metric, count, links, need, best or a next-hop word
+ *                  differs; a record carries the NEW values and installed =
+ *                  links > 0 && need <= links. OSPF_E_RANGE / state unchanged /
+ *                  retry, rebased roots, commit by swap, the preconditions on
+ *                  sw and "any failure leaves the state as it was" hold as
+ *                  there. The drained bits and the links are read from the
+ *                  LOADED graph, so an in-place node overload
+ *                  (ospf_update_nodes) + re-sweep is reported like any event.
+ *   copy_policy    the committed entries of `roots` in
+ *                  ospf_sweep_select_policy's layout ([n][P], nh
+ *                  [n][P][nh_words]); any output may be NULL.
+ *                  ospf_selstate_copy on a policy state answers metric /
+ *                  count / nh as well.
+ *   set_policy     replaces the two columns (offsets / nodes stay; the same
+ *                  checks; min_nexthop NULL: all unset). Nothing committed
+ *                  changes: the next update_policy, even with the same sweep,
+ *                  reports what the new attributes changed -- the delta of a
+ *                  prefix-attribute change without a topology event. A
+ *                  resolved UCMP result becomes stale, as after an update.
+ * ospf_selstate_ucmp / ospf_selstate_ucmp_copy run over a policy state too.
+ * There an announcer need not select itself (a better class behind it, or it
+ * is drained beside an undrained class-mate), so a selected next hop whose
+ * no-transit bit is set contributes its LEAF weight for the prefix, VOID when
+ * that is 0, and is never waited for ("UCMP over the policy
+ * selection").
+ * The wrong kind of state -- ospf_selstate_update on a policy state,
+ * update_policy / copy_policy / set_policy on a plain one -- is OSPF_E_INVAL,
+ * nothing changed. A root with more distinct neighbours than the LDS holds
+ * link counts for (8 bytes each): OSPF_E_RANGE from prime / update_policy. */
+typedef struct ospf_select_pchange {
+  uint32_t root, prefix, metric, count, links, need, best, installed;
+} ospf_select_pchange;
+int ospf_selstate_create_policy(ospf_ctx* ctx, const ospf_select_ptable* table,
+                                ospf_selstate** out);
+int ospf_selstate_update_policy(ospf_selstate* st, ospf_sweep* sw, uint32_t nh_words,
+                                ospf_select_pchange* changes, uint32_t* nh /*[cap][nh_words]*/,
+                                uint32_t cap, uint32_t* n_changes, uint32_t* rebased_roots,
+                                uint32_t cap_rebased, uint32_t* n_rebased);
+int ospf_selstate_copy_policy(ospf_selstate* st, const uint32_t* roots, uint32_t n,
+                              uint32_t nh_words, const ospf_select_pout* out);
+int ospf_selstate_set_policy(ospf_selstate* st, const uint32_t* pref, const uint32_t* min_nexthop);
 /* Time every launch unit alone on its stream: reps (>= 1) timed launches
  * after one untimed one; fills min(cap, n_launches) records. The sweep must
  * have run once. */
@@ -913,7 +968,8 @@ uint64_t ospf_spf_runs(const ospf_ctx* ctx);
  * ospf_sweep_select_policy_dev / ospf_sweep_select_policy /
  * ospf_msweep_select_policy (per part) / ospf_selstate_prime /
  * ospf_selstate_update / ospf_selstate_copy / ospf_selstate_ucmp /
- * ospf_selstate_ucmp_copy on this context fails with
+ * ospf_selstate_ucmp_copy / ospf_selstate_update_policy /
+ * ospf_selstate_copy_policy / ospf_selstate_set_policy on this context fails with
  * OSPF_E_DEVICE and does nothing (0 = off). Lets the caller's handling of a
  * device error be tested without a faulting GPU. */
 int ospf_inject_error(ospf_ctx* ctx, uint32_t after_calls);

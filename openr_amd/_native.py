@@ -45,6 +45,8 @@ ENGINE_SYMBOLS = [
     "ospf_selstate_create", "ospf_selstate_destroy", "ospf_selstate_last_error",
     "ospf_selstate_device_bytes", "ospf_selstate_prime", "ospf_selstate_update", "ospf_selstate_copy",
     "ospf_selstate_ucmp", "ospf_selstate_ucmp_copy", "ospf_selstate_ucmp_info",
+    "ospf_selstate_create_policy", "ospf_selstate_update_policy", "ospf_selstate_copy_policy",
+    "ospf_selstate_set_policy",
     "ospf_multi_open", "ospf_multi_close", "ospf_multi_last_error", "ospf_multi_size",
     "ospf_multi_ctx", "ospf_multi_load_graph", "ospf_msweep_create", "ospf_msweep_destroy",
     "ospf_msweep_run", "ospf_msweep_digests", "ospf_msweep_part", "ospf_msweep_owner",
@@ -60,6 +62,7 @@ DECISION_SYMBOLS = [
     "odl_last_decode_error", "odl_get_counters", "odl_last_engine_error", "odl_inject_engine_error",
     "odl_set_degrade", "odl_all_sources_select", "odl_all_sources_select_policy",
     "odl_track_select", "odl_select_delta", "odl_select_tracked",
+    "odl_track_select_policy", "odl_policy_delta", "odl_policy_tracked", "odl_set_tracked_attrs",
     "odl_all_sources_ucmp", "odl_ucmp_tracked", "odl_ucmp_host_loop",
 ]
 
@@ -249,6 +252,11 @@ def engine() -> C.CDLL:
         L.ospf_selstate_ucmp.argtypes = [vp, u32, vp, vp, u32, C.POINTER(u32)]
         L.ospf_selstate_ucmp_copy.argtypes = [vp, vp, u32, vp, vp, vp, vp, u64, C.POINTER(u64)]
         L.ospf_selstate_ucmp_info.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+        L.ospf_selstate_create_policy.argtypes = [vp, C.POINTER(ospf_select_ptable), C.POINTER(vp)]
+        L.ospf_selstate_update_policy.argtypes = [vp, vp, u32, vp, vp, u32, C.POINTER(u32), vp, u32,
+                                                  C.POINTER(u32)]
+        L.ospf_selstate_copy_policy.argtypes = [vp, vp, u32, u32, C.POINTER(ospf_select_pout)]
+        L.ospf_selstate_set_policy.argtypes = [vp, vp, vp]
         L.ospf_sweep_profile.argtypes = [vp, u32, vp, u32]
         L.ospf_sweep_graph_memsets.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.ospf_multi_open.argtypes = [vp, u32, C.POINTER(vp)]
@@ -291,6 +299,11 @@ def decision() -> C.CDLL:
         L.odl_select_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
                                        C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.odl_select_tracked.argtypes = [vp, cp, u32, u32, vp, vp, vp]
+        L.odl_track_select_policy.argtypes = [vp, cp, u32, vp, u32, i32]
+        L.odl_policy_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
+                                       C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.odl_policy_tracked.argtypes = [vp, cp, u32, u32, vp, vp, vp, vp, vp, vp, vp]
+        L.odl_set_tracked_attrs.argtypes = [vp, vp, u32]
         L.odl_all_sources_ucmp.argtypes = [vp, i32, vp, u32, vp, vp, C.POINTER(u32), C.POINTER(i32),
                                            C.POINTER(C.c_double)]
         L.odl_ucmp_tracked.argtypes = [vp, cp, u32, vp, vp, vp, C.POINTER(vp), C.POINTER(u64)]

@@ -432,6 +432,95 @@ int odl_all_sources_select(odl_ls* h, const char* prefixes_nl, uint32_t n_prefix
   }, -1);
 }
 
+namespace {
+// attribute sets (4 int64 each: path preference, source preference, distance,
+// minNexthop or INT64_MIN for unset) -> one list per prefix, parallel to `names`
+std::vector<std::vector<odl::LinkState::SelectAttr>> attrLists(
+    const std::vector<std::vector<std::string>>& names, const int64_t* attrs, uint32_t n_attrs) {
+  if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
+  std::vector<std::vector<odl::LinkState::SelectAttr>> at;
+  size_t used = 0;
+  for (const auto& ln : names) {
+    std::vector<odl::LinkState::SelectAttr> as;
+    for (size_t i = 0; i < ln.size(); ++i) {
+      if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than announcer names");
+      const int64_t* a = attrs + 4 * used++;
+      odl::LinkState::SelectAttr sa;
+      sa.pathPreference = a[0];
+      sa.sourcePreference = a[1];
+      sa.distance = a[2];
+      if (a[3] != std::numeric_limits<int64_t>::min()) sa.minNexthop = a[3];
+      as.push_back(sa);
+    }
+    at.push_back(std::move(as));
+  }
+  if (used != n_attrs) throw std::invalid_argument("more attribute sets than announcer names");
+  return at;
+}
+}  // namespace
+
+int odl_track_select_policy(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes,
+                            const int64_t* attrs, uint32_t n_attrs, int use_link_metric) {
+  return guard(h, [&]() -> int {
+    const auto names = prefixLines(prefixes_nl, n_prefixes);
+    h->ls.trackSelect(names, attrLists(names, attrs, n_attrs), use_link_metric != 0);
+    return 0;
+  }, -1);
+}
+
+int odl_set_tracked_attrs(odl_ls* h, const int64_t* attrs, uint32_t n_attrs) {
+  return guard(h, [&]() -> int {
+    h->ls.setTrackedAttrs(attrLists(h->ls.trackedPrefixes(), attrs, n_attrs));
+    return 0;
+  }, -1);
+}
+
+int odl_policy_delta(odl_ls* h, uint32_t* n_changes, uint32_t* n_rebased, uint32_t* nh_words,
+                     int* full, void** changes, void** nh, void** rebased) {
+  return guard(h, [&]() -> int {
+    if (!n_changes || !n_rebased || !nh_words || !full || !changes || !nh || !rebased)
+      throw std::invalid_argument("null output pointer");
+    *changes = *nh = *rebased = nullptr;
+    const auto d = h->ls.policyDelta();
+    static_assert(sizeof(odl::LinkState::PolicyChange) == 32, "odl_policy_change layout");
+    void* a = dupVec(d.changes);
+    void* b = nullptr;
+    void* c = nullptr;
+    try {
+      b = dupVec(d.nh);
+      c = dupVec(d.rebased);
+    } catch (...) {
+      std::free(a);
+      std::free(b);
+      throw;
+    }
+    *changes = a;
+    *nh = b;
+    *rebased = c;
+    *n_changes = (uint32_t)d.changes.size();
+    *n_rebased = (uint32_t)d.rebased.size();
+    *nh_words = d.words;
+    *full = d.full ? 1 : 0;
+    return 0;
+  }, -1);
+}
+
+int odl_policy_tracked(odl_ls* h, const char* nodes_nl, uint32_t n, uint32_t nh_words,
+                       uint32_t* metric, uint32_t* count, uint32_t* nh, uint32_t* links,
+                       uint32_t* need, uint32_t* best, uint8_t* installed) {
+  return guard(h, [&]() -> int {
+    const auto r = h->ls.policyTracked(splitNl(nodes_nl ? nodes_nl : "", n), nh_words);
+    if (metric) std::copy(r.metric.begin(), r.metric.end(), metric);
+    if (count) std::copy(r.count.begin(), r.count.end(), count);
+    if (nh) std::copy(r.nh.begin(), r.nh.end(), nh);
+    if (links) std::copy(r.links.begin(), r.links.end(), links);
+    if (need) std::copy(r.need.begin(), r.need.end(), need);
+    if (best) std::copy(r.best.begin(), r.best.end(), best);
+    if (installed) std::copy(r.installed.begin(), r.installed.end(), installed);
+    return 0;
+  }, -1);
+}
+
 int odl_all_sources_select_policy(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes,
                                   const int64_t* attrs, uint32_t n_attrs, int use_link_metric,
                                   uint32_t nh_words, uint32_t* nh_words_needed, uint32_t* metric,

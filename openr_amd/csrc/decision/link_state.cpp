@@ -1228,21 +1228,20 @@ LinkState::SelectResult LinkState::allSourcesSelectImpl(
 }
 
 // ---------------------------------------------------------------- select policy
-LinkState::PolicyResult LinkState::allSourcesSelect(
-    const std::vector<std::vector<std::string>>& prefixes,
-    const std::vector<std::vector<SelectAttr>>& attrs, bool useLinkMetric, uint32_t nhWords) {
-  snapshot();
+void LinkState::policyTable(const std::vector<std::vector<std::string>>& prefixes,
+                            const std::vector<std::vector<SelectAttr>>& attrs, const char* who,
+                            std::vector<std::vector<uint32_t>>& ann,
+                            std::vector<std::vector<uint32_t>>& pref,
+                            std::vector<std::vector<uint32_t>>& mnh) const {
   if (attrs.size() != prefixes.size())
-    throw std::invalid_argument("allSourcesSelect: one attribute list per prefix");
-  const uint32_t need = selectWords();
-  if (nhWords && nhWords < need)
-    throw std::invalid_argument("allSourcesSelect: nhWords " + std::to_string(nhWords) +
-                                " below the widest node's " + std::to_string(need));
+    throw std::invalid_argument(std::string(who) + ": one attribute list per prefix");
   const size_t P = prefixes.size();
-  std::vector<std::vector<uint32_t>> ann(P), pref(P), mnh(P);
+  ann.assign(P, {});
+  pref.assign(P, {});
+  mnh.assign(P, {});
   for (size_t p = 0; p < P; ++p) {
     if (attrs[p].size() != prefixes[p].size())
-      throw std::invalid_argument("allSourcesSelect: one attribute set per announcer");
+      throw std::invalid_argument(std::string(who) + ": one attribute set per announcer");
     // names -> ids: unknown names dropped with their attributes, the first
     // occurrence of a name counts; ascending by id
     std::vector<std::pair<uint32_t, size_t>> ent;  // (id, position in the prefix's list)
@@ -1279,6 +1278,18 @@ LinkState::PolicyResult LinkState::allSourcesSelect(
       mnh[p].push_back((uint32_t)v);
     }
   }
+}
+
+LinkState::PolicyResult LinkState::allSourcesSelect(
+    const std::vector<std::vector<std::string>>& prefixes,
+    const std::vector<std::vector<SelectAttr>>& attrs, bool useLinkMetric, uint32_t nhWords) {
+  snapshot();
+  const uint32_t need = selectWords();
+  if (nhWords && nhWords < need)
+    throw std::invalid_argument("allSourcesSelect: nhWords " + std::to_string(nhWords) +
+                                " below the widest node's " + std::to_string(need));
+  std::vector<std::vector<uint32_t>> ann, pref, mnh;
+  policyTable(prefixes, attrs, "allSourcesSelect", ann, pref, mnh);
   const uint32_t W = nhWords ? nhWords : need;
   return guarded([&] { return allSourcesPolicyImpl(ann, pref, mnh, useLinkMetric, W); });
 }
@@ -1442,6 +1453,26 @@ void LinkState::trackPull() {
   const size_t V = trackNames_.size(), P = trackPrefixes_.size(), W = trackWords_;
   std::vector<uint32_t> ids(V);
   for (size_t i = 0; i < V; ++i) ids[i] = (uint32_t)i;
+  if (trackPolicy_) {
+    PolicyResult r;
+    r.prefixes = (uint32_t)P;
+    r.words = (uint32_t)W;
+    r.metric.assign(V * P, kInf);
+    r.count.assign(V * P, 0);
+    r.links.assign(V * P, 0);
+    r.need.assign(V * P, 0);
+    r.best.assign(V * P, kInf);
+    r.nh.assign(V * P * W, 0);
+    const ospf_select_pout o{r.metric.data(), r.count.data(), r.nh.data(),
+                             r.links.data(),  r.need.data(),  r.best.data()};
+    const int rc = ospf_selstate_copy_policy(selstate_, ids.data(), (uint32_t)V, (uint32_t)W, &o);
+    r.installed.assign(V * P, 0);
+    for (size_t i = 0; i < V * P; ++i) r.installed[i] = r.links[i] > 0 && r.need[i] <= r.links[i];
+    trackDev_ = false;
+    trackHostOk_ = rc == OSPF_OK;
+    if (trackHostOk_) trackHostP_ = std::move(r);
+    return;
+  }
   SelectResult r;
   r.prefixes = (uint32_t)P;
   r.words = (uint32_t)W;
@@ -1462,7 +1493,11 @@ void LinkState::trackPrime() {
   trackDropDev();
   trackHostOk_ = false;
   trackHost_ = SelectResult{};
+  trackHostP_ = PolicyResult{};
+  trackAttrsMoved_ = false;
   const uint32_t W = selectWords();
+  std::vector<std::vector<uint32_t>> pann, pref, mnh;
+  if (trackPolicy_) policyTable(trackPrefixes_, trackAttrs_, "trackSelect", pann, pref, mnh);
   if (!hostRun(trackMetric_) && devices_.size() == 1 && V) {
     prefetchAllSources(trackMetric_);
     std::vector<uint32_t> off(ann.size() + 1, 0), nodes;
@@ -1471,7 +1506,18 @@ void LinkState::trackPrime() {
       off[p + 1] = (uint32_t)nodes.size();
     }
     const ospf_select_table t{(uint32_t)ann.size(), off.data(), nodes.data()};
-    int rc = ospf_selstate_create(engine_, &t, &selstate_);
+    int rc;
+    if (trackPolicy_) {
+      std::vector<uint32_t> prefs, mins;
+      for (size_t p = 0; p < ann.size(); ++p) {
+        prefs.insert(prefs.end(), pref[p].begin(), pref[p].end());
+        mins.insert(mins.end(), mnh[p].begin(), mnh[p].end());
+      }
+      const ospf_select_ptable pt{t.n_prefixes, off.data(), nodes.data(), prefs.data(), mins.data()};
+      rc = ospf_selstate_create_policy(engine_, &pt, &selstate_);
+    } else {
+      rc = ospf_selstate_create(engine_, &t, &selstate_);
+    }
     if (rc != OSPF_OK) throw EngineError(rc, ospf_last_error(engine_));
     rc = ospf_selstate_prime(selstate_, sweep_);
     if (rc != OSPF_OK) {
@@ -1481,7 +1527,8 @@ void LinkState::trackPrime() {
     }
     trackDev_ = true;
   } else {
-    trackHost_ = allSourcesSelectImpl(ann, trackMetric_, W);
+    if (trackPolicy_) trackHostP_ = allSourcesPolicyImpl(ann, pref, mnh, trackMetric_, W);
+    else trackHost_ = allSourcesSelectImpl(ann, trackMetric_, W);
     trackHostOk_ = true;
   }
   trackNames_ = csr_->names;
@@ -1494,13 +1541,183 @@ void LinkState::trackPrime() {
 void LinkState::trackSelect(const std::vector<std::vector<std::string>>& prefixes,
                             bool useLinkMetric) {
   trackPrefixes_ = prefixes;
+  trackAttrs_.clear();
+  trackPolicy_ = false;
   trackMetric_ = useLinkMetric;
   tracking_ = true;
   guarded([&] { trackPrime(); });
 }
 
+void LinkState::trackSelect(const std::vector<std::vector<std::string>>& prefixes,
+                            const std::vector<std::vector<SelectAttr>>& attrs, bool useLinkMetric) {
+  snapshot();
+  std::vector<std::vector<uint32_t>> ann, pref, mnh;
+  policyTable(prefixes, attrs, "trackSelect", ann, pref, mnh);  // the argument checks
+  trackPrefixes_ = prefixes;
+  trackAttrs_ = attrs;
+  trackPolicy_ = true;
+  trackMetric_ = useLinkMetric;
+  tracking_ = true;
+  guarded([&] { trackPrime(); });
+}
+
+void LinkState::setTrackedAttrs(const std::vector<std::vector<SelectAttr>>& attrs) {
+  if (!tracking_ || !trackPolicy_)
+    throw std::logic_error("setTrackedAttrs: no table tracked with attributes (trackSelect)");
+  snapshot();
+  std::vector<std::vector<uint32_t>> ann, pref, mnh;
+  policyTable(trackPrefixes_, attrs, "setTrackedAttrs", ann, pref, mnh);
+  trackAttrs_ = attrs;
+  trackAttrsMoved_ = true;
+  ucmpDev_ = ucmpHostOk_ = false;
+  // the device state's columns are replaced by the next policyDelta, once it
+  // knows that the state's table is still the snapshot's (trackAttrsMoved_)
+}
+
+LinkState::PolicyDelta LinkState::policyDelta() {
+  if (!tracking_ || !trackPolicy_)
+    throw std::logic_error("policyDelta: no table tracked with attributes (trackSelect)");
+  return guarded([&] { return policyDeltaImpl(); });
+}
+
+LinkState::PolicyDelta LinkState::policyDeltaImpl() {
+  snapshot();
+  PolicyDelta out;
+  const size_t V = csr_->names.size(), P = trackPrefixes_.size();
+  const uint32_t W = selectWords();
+  out.words = W;
+  if (csr_->names != trackNames_ || (!trackDev_ && !trackHostOk_)) {
+    trackPrime();
+    out.full = true;
+    return out;
+  }
+  const bool dev = !hostRun(trackMetric_) && devices_.size() == 1;
+  if (dev && trackDev_) {
+    prefetchAllSources(trackMetric_);  // re-sweeps when the version moved
+    if (trackAttrsMoved_) {
+      // the node names are the tracked ones here, so the ids are the state's
+      std::vector<std::vector<uint32_t>> ann, pref, mnh;
+      policyTable(trackPrefixes_, trackAttrs_, "policyDelta", ann, pref, mnh);
+      std::vector<uint32_t> prefs, mins;
+      for (size_t p = 0; p < ann.size(); ++p) {
+        prefs.insert(prefs.end(), pref[p].begin(), pref[p].end());
+        mins.insert(mins.end(), mnh[p].begin(), mnh[p].end());
+      }
+      const int rc = ospf_selstate_set_policy(selstate_, prefs.data(), mins.data());
+      if (rc != OSPF_OK) throw EngineError(rc, ospf_selstate_last_error(selstate_));
+    }
+    uint32_t cap = 1024, capReb = 64, n = 0, nReb = 0;
+    std::vector<ospf_select_pchange> recs;
+    for (;;) {
+      recs.resize(cap);
+      out.nh.assign((size_t)cap * W, 0);
+      out.rebased.assign(capReb, 0);
+      const int rc = ospf_selstate_update_policy(selstate_, sweep_, W, recs.data(), out.nh.data(), cap,
+                                                 &n, out.rebased.data(), capReb, &nReb);
+      if (rc == OSPF_OK) break;
+      if (rc != OSPF_E_RANGE) throw EngineError(rc, ospf_selstate_last_error(selstate_));
+      cap = std::max(cap, n);  // the state is unchanged: the same call, large enough
+      capReb = std::max(capReb, nReb);
+    }
+    out.changes.resize(n);
+    for (uint32_t i = 0; i < n; ++i)
+      out.changes[i] = PolicyChange{recs[i].root, recs[i].prefix, recs[i].metric, recs[i].count,
+                                    recs[i].links, recs[i].need,   recs[i].best,   recs[i].installed};
+    out.nh.resize((size_t)n * W);
+    out.rebased.resize(nReb);
+    std::sort(out.rebased.begin(), out.rebased.end());
+  } else {
+    if (trackDev_) trackPull();  // the host takes over with the device's baseline
+    if (!trackHostOk_) {
+      trackPrime();
+      out.full = true;
+      return out;
+    }
+    trackDropDev();
+    std::vector<std::vector<uint32_t>> ann, pref, mnh;
+    policyTable(trackPrefixes_, trackAttrs_, "policyDelta", ann, pref, mnh);
+    PolicyResult now = allSourcesPolicyImpl(ann, pref, mnh, trackMetric_, W);
+    const PolicyResult& was = trackHostP_;
+    for (uint32_t v = 0; v < V; ++v) {
+      if (nbrsOf(v) != trackNbrs_[v]) {
+        out.rebased.push_back(v);
+        continue;
+      }
+      for (size_t p = 0; p < P; ++p) {
+        const size_t i = v * P + p;
+        bool ch = now.metric[i] != was.metric[i] || now.count[i] != was.count[i] ||
+                  now.links[i] != was.links[i] || now.need[i] != was.need[i] ||
+                  now.best[i] != was.best[i];
+        for (uint32_t w = 0; w < std::max(W, was.words) && !ch; ++w)
+          ch = (w < W ? now.nh[i * W + w] : 0u) != (w < was.words ? was.nh[i * was.words + w] : 0u);
+        if (!ch) continue;
+        out.changes.push_back(PolicyChange{v, (uint32_t)p, now.metric[i], now.count[i], now.links[i],
+                                           now.need[i], now.best[i], now.installed[i]});
+        out.nh.insert(out.nh.end(), now.nh.begin() + i * W, now.nh.begin() + (i + 1) * W);
+      }
+    }
+    trackHostP_ = std::move(now);
+  }
+  trackWords_ = W;
+  for (uint32_t v : out.rebased) trackNbrs_[v] = nbrsOf(v);
+  trackVersion_ = snapVersion_;
+  trackAttrsMoved_ = false;
+  return out;
+}
+
+LinkState::PolicyResult LinkState::policyTracked(const std::vector<std::string>& nodes,
+                                                 uint32_t nhWords) {
+  if (!tracking_ || !trackPolicy_)
+    throw std::logic_error("policyTracked: no table tracked with attributes (trackSelect)");
+  if (!trackDev_ && !trackHostOk_) throw std::logic_error("policyTracked: no baseline (policyDelta)");
+  const uint32_t W = nhWords ? nhWords : trackWords_;
+  if (W < trackWords_)
+    throw std::invalid_argument("policyTracked: nhWords " + std::to_string(W) +
+                                " below the baseline's " + std::to_string(trackWords_));
+  const auto ids = trackIds(nodes, "policyTracked");
+  return guarded([&] {
+    const size_t n = ids.size(), P = trackPrefixes_.size();
+    PolicyResult r;
+    r.prefixes = (uint32_t)P;
+    r.words = W;
+    r.metric.assign(n * P, kInf);
+    r.count.assign(n * P, 0);
+    r.links.assign(n * P, 0);
+    r.need.assign(n * P, 0);
+    r.best.assign(n * P, kInf);
+    r.nh.assign(n * P * W, 0);
+    r.installed.assign(n * P, 0);
+    if (trackDev_) {
+      const ospf_select_pout o{r.metric.data(), r.count.data(), r.nh.data(),
+                               r.links.data(),  r.need.data(),  r.best.data()};
+      const int rc = ospf_selstate_copy_policy(selstate_, ids.data(), (uint32_t)n, W, &o);
+      if (rc != OSPF_OK) throw EngineError(rc, ospf_selstate_last_error(selstate_));
+    } else {
+      if (!trackHostOk_) throw std::logic_error("policyTracked: the baseline was lost (policyDelta)");
+      const PolicyResult& h = trackHostP_;
+      for (size_t i = 0; i < n; ++i) {
+        const size_t v = ids[i];
+        auto put = [&](const std::vector<uint32_t>& src, std::vector<uint32_t>& dst) {
+          std::copy(src.begin() + v * P, src.begin() + (v + 1) * P, dst.begin() + i * P);
+        };
+        put(h.metric, r.metric);
+        put(h.count, r.count);
+        put(h.links, r.links);
+        put(h.need, r.need);
+        put(h.best, r.best);
+        for (size_t p = 0; p < P; ++p)
+          std::copy(h.nh.begin() + (v * P + p) * h.words, h.nh.begin() + (v * P + p + 1) * h.words,
+                    r.nh.begin() + (i * P + p) * W);
+      }
+    }
+    for (size_t i = 0; i < n * P; ++i) r.installed[i] = r.links[i] > 0 && r.need[i] <= r.links[i];
+    return r;
+  });
+}
+
 LinkState::SelectDelta LinkState::selectDelta() {
   if (!tracking_) throw std::logic_error("selectDelta: no tracked table (trackSelect)");
+  if (trackPolicy_) throw std::logic_error("selectDelta: the table is tracked with attributes (policyDelta)");
   return guarded([&] { return selectDeltaImpl(); });
 }
 
@@ -1575,6 +1792,8 @@ LinkState::SelectDelta LinkState::selectDeltaImpl() {
 LinkState::SelectResult LinkState::selectTracked(const std::vector<std::string>& nodes,
                                                  uint32_t nhWords) {
   if (!tracking_) throw std::logic_error("selectTracked: no tracked table (trackSelect)");
+  if (trackPolicy_)
+    throw std::logic_error("selectTracked: the table is tracked with attributes (policyTracked)");
   if (!trackDev_ && !trackHostOk_) throw std::logic_error("selectTracked: no baseline (selectDelta)");
   const uint32_t W = nhWords ? nhWords : trackWords_;
   if (W < trackWords_)
@@ -1619,9 +1838,10 @@ LinkState::SelectResult LinkState::selectTracked(const std::vector<std::string>&
 void LinkState::trackCurrent(const char* who) {
   if (!tracking_) throw std::logic_error(std::string(who) + ": no tracked table (trackSelect)");
   snapshot();
-  if (snapVersion_ != trackVersion_ || csr_->names != trackNames_ || (!trackDev_ && !trackHostOk_))
-    throw std::logic_error(std::string(who) +
-                           ": the tracked selection is older than the topology (selectDelta)");
+  if (snapVersion_ != trackVersion_ || csr_->names != trackNames_ || (!trackDev_ && !trackHostOk_) ||
+      trackAttrsMoved_)
+    throw std::logic_error(std::string(who) + ": the tracked selection is older than the topology" +
+                           " or its attributes (selectDelta / policyDelta)");
 }
 
 std::vector<std::vector<int64_t>> LinkState::trackLeafWeights(
@@ -1660,6 +1880,11 @@ LinkState::UcmpView LinkState::ucmpHostImpl(UcmpAlgo algo, const std::vector<std
                                             const std::vector<std::vector<int64_t>>& w,
                                             const std::vector<uint32_t>& ids) {
   const size_t P = ann.size();
+  std::vector<std::vector<uint32_t>> pann, pref, mnh;  // a policy table: its class ranks
+  if (trackPolicy_) {
+    policyTable(trackPrefixes_, trackAttrs_, "allSourcesUcmp", pann, pref, mnh);
+    if (pann != ann) throw std::logic_error("allSourcesUcmp: the class ranks are not the table's");
+  }
   UcmpView out;
   out.prefixes = (uint32_t)P;
   out.weight.assign(ids.size() * P, 0);
@@ -1676,9 +1901,21 @@ LinkState::UcmpView LinkState::ucmpHostImpl(UcmpAlgo algo, const std::vector<std
       Metric shortest = std::numeric_limits<Metric>::max();
       std::unordered_map<std::string, int64_t> leaves;
       bool zero = false;
+      // under the policy the walk starts from its filtered set: the reached
+      // announcers of the best class, the drained ones dropped unless all are
+      uint32_t top = kInf;
+      bool undrained = false;
+      if (trackPolicy_) {
+        for (size_t k = 0; k < ann[p].size(); ++k)
+          if (res.find(csr_->names[ann[p][k]]) != res.end()) top = std::min(top, pref[p][k]);
+        for (size_t k = 0; k < ann[p].size(); ++k)
+          undrained |= pref[p][k] == top && !csr_->noTransit[ann[p][k]] &&
+                       res.find(csr_->names[ann[p][k]]) != res.end();
+      }
       for (size_t k = 0; k < ann[p].size(); ++k) {
         const auto it = res.find(csr_->names[ann[p][k]]);
         if (it == res.end()) continue;
+        if (trackPolicy_ && (pref[p][k] != top || (undrained && csr_->noTransit[ann[p][k]]))) continue;
         const Metric d = it->second.metric();
         if (d > shortest) continue;
         if (d < shortest) {

@@ -621,6 +621,36 @@ class LinkState {
   void trackSelect(const std::vector<std::vector<std::string>>& prefixes, bool useLinkMetric = true);
   SelectDelta selectDelta();
   SelectResult selectTracked(const std::vector<std::string>& nodes, uint32_t nhWords = 0);
+  // The same over the policy selection (allSourcesSelect(prefixes, attrs)):
+  // the reference diffs the routes the policy produced and walks UCMP from
+  // the announcers the policy kept. trackSelect with attributes stores that
+  // selection as the baseline (on the device: ospf_selstate_create_policy);
+  // policyDelta is selectDelta for it -- an entry changed when any of metric,
+  // count, links, need, best or a next-hop word differs -- and policyTracked
+  // is selectTracked. setTrackedAttrs replaces the attributes (the same
+  // announcer names per prefix): nothing stored changes, the next policyDelta
+  // reports what the new attributes changed, with or without a topology event.
+  // A table tracked with attributes refuses selectDelta / selectTracked
+  // (std::logic_error), one tracked without refuses policyDelta /
+  // policyTracked / setTrackedAttrs. allSourcesUcmp / ucmpTracked /
+  // ucmpHostLoop on such a table run over the policy selection; the host loop
+  // walks from the policy's filtered min-cost set. Host path, multi-device
+  // and degraded behaviour are selectDelta's.
+  struct PolicyChange {
+    uint32_t node, prefix, metric, count, links, need, best, installed;
+  };
+  struct PolicyDelta {
+    uint32_t words = 0;
+    std::vector<PolicyChange> changes;
+    std::vector<uint32_t> nh;       // [changes][words]
+    std::vector<uint32_t> rebased;  // node ids
+    bool full = false;
+  };
+  void trackSelect(const std::vector<std::vector<std::string>>& prefixes,
+                   const std::vector<std::vector<SelectAttr>>& attrs, bool useLinkMetric = true);
+  PolicyDelta policyDelta();
+  PolicyResult policyTracked(const std::vector<std::string>& nodes, uint32_t nhWords = 0);
+  void setTrackedAttrs(const std::vector<std::vector<SelectAttr>>& attrs);
   // UCMP weights of every node for every prefix of the tracked table:
   // SpfSolver::getNodeUcmpResult -> resolveUcmpWeights (SpfSolver.cpp:1091-1161,
   // LinkState.cpp:913-1033) for all nodes at once. leafWeights is parallel to
@@ -882,8 +912,19 @@ class LinkState {
                                     const std::vector<std::vector<uint32_t>>& pref,
                                     const std::vector<std::vector<uint32_t>>& mnh,
                                     bool useLinkMetric, uint32_t W);
+  // names -> ids (unknown names dropped with their attributes, the first
+  // occurrence counts, ascending), class ranks and clamped thresholds
+  void policyTable(const std::vector<std::vector<std::string>>& prefixes,
+                   const std::vector<std::vector<SelectAttr>>& attrs, const char* who,
+                   std::vector<std::vector<uint32_t>>& ann, std::vector<std::vector<uint32_t>>& pref,
+                   std::vector<std::vector<uint32_t>>& mnh) const;
   // ---- trackSelect ----
   bool tracking_ = false, trackMetric_ = true;
+  bool trackPolicy_ = false;       // tracked with attributes: the policy selection
+  bool trackAttrsMoved_ = false;   // setTrackedAttrs since the last policyDelta
+  std::vector<std::vector<SelectAttr>> trackAttrs_;  // parallel to trackPrefixes_
+  PolicyResult trackHostP_;        // the host baseline of a policy table
+  PolicyDelta policyDeltaImpl();
   std::vector<std::vector<std::string>> trackPrefixes_;  // by name: ids move with the name set
   std::vector<std::string> trackNames_;                  // node names of the baseline
   std::vector<std::vector<uint32_t>> trackNbrs_;         // their distinct neighbours (bit order)

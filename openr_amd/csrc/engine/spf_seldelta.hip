@@ -253,23 +253,24 @@ void release(ospf_selstate* st) {
     b = ospf_selstate::Buf{};
   }
   (void)hipFree(st->d_tab);
+  (void)hipFree(st->d_pol);
   (void)hipFree(st->d_roots);
   (void)hipFree(st->d_cnt);
   (void)hipFree(st->d_chg);
   (void)hipFree(st->d_chg_nh);
   (void)hipFree(st->d_reb);
-  st->d_tab = st->d_roots = st->d_cnt = st->d_chg_nh = st->d_reb = nullptr;
+  st->d_tab = st->d_pol = st->d_roots = st->d_cnt = st->d_chg_nh = st->d_reb = nullptr;
   st->d_chg = nullptr;
   st->chg_cap = st->chg_nh_words = st->reb_cap = 0;
   st->device_bytes = 0;
   st->primed = false;
 }
 
-// sw's selection into the shadow buffer; with `compare` the entries that
-// differ from the committed buffer's and the rebased roots are listed (up to
-// the caps) and counted. Nothing is committed.
-int write_shadow(ospf_selstate* st, ospf_sweep* sw, bool compare, uint32_t nh_words, bool want_nh,
-                 uint32_t cap, uint32_t cap_reb, uint32_t counts[2]) {
+}  // namespace
+
+int ospf_int::selst::write_shadow(ospf_selstate* st, ospf_sweep* sw, bool compare,
+                                  uint32_t nh_words, bool want_nh, uint32_t cap, uint32_t cap_reb,
+                                  uint32_t counts[2]) {
   ospf_ctx* c = st->c;
   const uint32_t V = st->V, P = st->P;
   ospf_selstate::Buf& nb = st->b[st->cur ^ 1];
@@ -285,7 +286,7 @@ int write_shadow(ospf_selstate* st, ospf_sweep* sw, bool compare, uint32_t nh_wo
   for (uint32_t r = 0; r < V; ++r) {
     nb.h_off[r] = words;
     nb.h_w[r] = sw->row_w[r];
-    words += (uint64_t)P * (2u + sw->row_w[r]);
+    words += (uint64_t)P * (st->hdr + sw->row_w[r]);
   }
   int rc;
   if ((rc = grow(st, &nb.data, &nb.data_words, words))) return rc;
@@ -299,12 +300,20 @@ int write_shadow(ospf_selstate* st, ospf_sweep* sw, bool compare, uint32_t nh_wo
     STCHK(st, hipMemcpy(nb.dn, c->h_dn.data(), c->h_dn.size() * 4, hipMemcpyHostToDevice));
   STCHK(st, hipMemcpy(st->d_roots, sw->roots.data(), (size_t)V * 4, hipMemcpyHostToDevice));
   if (compare) {
-    if ((rc = grow(st, &st->d_chg, &st->chg_cap, cap))) return rc;
+    // a policy record is two uint4
+    if ((rc = grow(st, &st->d_chg, &st->chg_cap, (size_t)cap * (st->policy ? 2u : 1u)))) return rc;
     if (want_nh && (rc = grow(st, &st->d_chg_nh, &st->chg_nh_words, (size_t)cap * nh_words))) return rc;
     if ((rc = grow(st, &st->d_reb, &st->reb_cap, cap_reb))) return rc;
   }
   const uint32_t zero[2] = {0, 0};
   STCHK(st, hipMemcpy(st->d_cnt, zero, sizeof(zero), hipMemcpyHostToDevice));
+  if (!V || !P) return OSPF_OK;  // no entry: nothing to store or compare
+  if (st->policy) {
+    if ((rc = policy_delta_launch(st, sw, compare, nh_words, want_nh, cap, cap_reb))) return rc;
+    STCHK(st, hipDeviceSynchronize());
+    STCHK(st, hipMemcpy(counts, st->d_cnt, 8, hipMemcpyDeviceToHost));
+    return OSPF_OK;
+  }
   SdArgs a{};
   a.rows = sw->d_sel_rows;
   a.roots = st->d_roots;
@@ -332,7 +341,6 @@ int write_shadow(ospf_selstate* st, ospf_sweep* sw, bool compare, uint32_t nh_wo
   a.counters = st->d_cnt;
   // a wave per 64 prefixes of the root, at most 4; roots beyond the grid by stride
   const uint32_t waves = std::min(4u, (P + 63u) / 64u);
-  if (!V || !P) return OSPF_OK;  // no entry: nothing to store or compare
   hipLaunchKernelGGL(seldelta_kernel, dim3(std::min(V, 1u << 20)), dim3(64u * waves), 0, nullptr, a);
   STCHK(st, hipGetLastError());
   STCHK(st, hipDeviceSynchronize());
@@ -340,8 +348,7 @@ int write_shadow(ospf_selstate* st, ospf_sweep* sw, bool compare, uint32_t nh_wo
   return OSPF_OK;
 }
 
-// what makes `sw` unusable for the state (null: usable)
-const char* sweep_error(const ospf_selstate* st, const ospf_sweep* sw) {
+const char* ospf_int::selst::sweep_error(const ospf_selstate* st, const ospf_sweep* sw) {
   if (sw->c != st->c) return "selstate: the sweep belongs to another context";
   if (!sw->ran) return "selstate: the sweep has not run";
   if (sw->V != st->V) return "selstate: the sweep's graph has another node count";
@@ -352,29 +359,21 @@ const char* sweep_error(const ospf_selstate* st, const ospf_sweep* sw) {
   return nullptr;
 }
 
-// the committed selection is sw's: what a consumer of the state checks it by
-void committed(ospf_selstate* st, const ospf_sweep* sw) {
+void ospf_int::selst::committed(ospf_selstate* st, const ospf_sweep* sw) {
   st->gen = sw->gen;
   st->hop = (sw->opts.flags & OSPF_HOP_COUNT) != 0;
   ++st->serial;
 }
 
-uint32_t max_words(const ospf_sweep* sw) {
+uint32_t ospf_int::selst::max_words(const ospf_sweep* sw) {
   uint32_t mw = 0;
   for (uint32_t r : sw->roots) mw = std::max(mw, sw->row_w[r]);
   return mw;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ospf_selstate_create(ospf_ctx* c, const ospf_select_table* t, ospf_selstate** out) {
-  if (!c || !out) return OSPF_E_INVAL;
-  *out = nullptr;
-  if (!c->loaded) return fail(c, OSPF_E_NOGRAPH, "no graph loaded");
+int ospf_int::selst::create(ospf_ctx* c, const ospf_select_table* t, const ospf_select_ptable* pol,
+                            ospf_selstate** out) {
   const uint32_t V = c->info.n_nodes;
-  if (const char* bad = select_table_check(t, V)) return fail(c, OSPF_E_INVAL, bad);
   ospf_selstate* st = new (std::nothrow) ospf_selstate();
   if (!st) return OSPF_E_NOMEM;
   st->c = c;
@@ -387,6 +386,13 @@ int ospf_selstate_create(ospf_ctx* c, const ospf_select_table* t, ospf_selstate*
   } else {
     st->t_off.assign(1, 0u);
   }
+  if (pol) {
+    st->policy = true;
+    st->hdr = 5;
+    const size_t A = st->t_nodes.size();
+    if (A) st->t_pref.assign(pol->pref, pol->pref + A);
+    if (A && pol->min_nexthop) st->t_mnh.assign(pol->min_nexthop, pol->min_nexthop + A);
+  }
   auto setup = [&]() -> int {
     STCHK(st, hipSetDevice(c->device));
     size_t have = 0;
@@ -396,6 +402,13 @@ int ospf_selstate_create(ospf_ctx* c, const ospf_select_table* t, ospf_selstate*
     if (!st->t_nodes.empty())
       STCHK(st, hipMemcpy(st->d_tab + P + 1, st->t_nodes.data(), st->t_nodes.size() * 4,
                           hipMemcpyHostToDevice));
+    if (st->policy) {
+      const size_t A = st->t_nodes.size();
+      if ((rc = grow(st, &st->d_pol, &(have = 0), 2 * A))) return rc;
+      if (A) STCHK(st, hipMemcpy(st->d_pol, st->t_pref.data(), A * 4, hipMemcpyHostToDevice));
+      if (!st->t_mnh.empty())
+        STCHK(st, hipMemcpy(st->d_pol + A, st->t_mnh.data(), A * 4, hipMemcpyHostToDevice));
+    }
     if ((rc = grow(st, &st->d_roots, &(have = 0), V))) return rc;
     if ((rc = grow(st, &st->d_cnt, &(have = 0), 2))) return rc;
     for (auto& b : st->b) {
@@ -417,6 +430,16 @@ int ospf_selstate_create(ospf_ctx* c, const ospf_select_table* t, ospf_selstate*
   };
   *out = st;
   return OSPF_OK;
+}
+
+extern "C" {
+
+int ospf_selstate_create(ospf_ctx* c, const ospf_select_table* t, ospf_selstate** out) {
+  if (!c || !out) return OSPF_E_INVAL;
+  *out = nullptr;
+  if (!c->loaded) return fail(c, OSPF_E_NOGRAPH, "no graph loaded");
+  if (const char* bad = select_table_check(t, c->info.n_nodes)) return fail(c, OSPF_E_INVAL, bad);
+  return create(c, t, nullptr, out);
 }
 
 int ospf_selstate_destroy(ospf_selstate* st) {
@@ -458,6 +481,8 @@ int ospf_selstate_update(ospf_selstate* st, ospf_sweep* sw, uint32_t nh_words,
     return OSPF_E_INVAL;
   *n_changes = *n_rebased = 0;
   if (injected(st->c)) return stfail(st, OSPF_E_DEVICE, st->c->err);
+  if (st->policy)
+    return stfail(st, OSPF_E_INVAL, "selstate: a policy state is updated by ospf_selstate_update_policy");
   if (!st->primed) return stfail(st, OSPF_E_INVAL, "selstate: update before prime");
   if (const char* bad = sweep_error(st, sw)) return stfail(st, OSPF_E_INVAL, bad);
   if (nh_words < max_words(sw))
@@ -502,7 +527,7 @@ int ospf_selstate_copy(ospf_selstate* st, const uint32_t* roots, uint32_t n, uin
   std::vector<uint32_t> blk;
   for (uint32_t i = 0; i < n; ++i) {
     const uint32_t r = roots[i], W = b.h_w[r];
-    blk.resize(P * (2u + W));
+    blk.resize(P * (st->hdr + W));
     STCHK(st, hipMemcpy(blk.data(), b.data + b.h_off[r], blk.size() * 4, hipMemcpyDeviceToHost));
     if (metric) std::memcpy(metric + i * P, blk.data(), P * 4);
     if (count) std::memcpy(count + i * P, blk.data() + P, P * 4);
@@ -510,7 +535,7 @@ int ospf_selstate_copy(ospf_selstate* st, const uint32_t* roots, uint32_t n, uin
       uint32_t* dst = nh + i * P * nh_words;
       std::memset(dst, 0, P * nh_words * 4);
       for (size_t p = 0; p < P; ++p)
-        std::memcpy(dst + p * nh_words, blk.data() + 2 * P + p * W, (size_t)W * 4);
+        std::memcpy(dst + p * nh_words, blk.data() + st->hdr * P + p * W, (size_t)W * 4);
     }
   }
   return OSPF_OK;

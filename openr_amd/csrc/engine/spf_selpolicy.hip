@@ -23,7 +23,7 @@
 //
 // Out of scope (include/openr_spf.h says so too): SR_MPLS per-destination
 // next hops, K_SHORTEST_DISTANCE_2 and PER_AREA_SHORTEST_DISTANCE, BGP metric
-// vectors, several areas, a policy table in ospf_selstate_*.
+// vectors, several areas. (A policy table in ospf_selstate_*: spf_seldelta_policy.hip.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -53,39 +53,6 @@ struct PolicyArgs {
   const uint32_t* dn_off;
   uint32_t *o_metric, *o_count, *o_nh, *o_links, *o_need, *o_best;
 };
-
-// c[0 .. ns) of root r into LDS as u16 (the first ns halves of `lds`); lds
-// holds 2 * cap words. Block-wide, with barriers.
-__device__ __forceinline__ void build_links(const PolicyArgs& a, uint32_t r, uint32_t ns,
-                                            uint32_t* lds) {
-  uint32_t* minw = lds;
-  uint32_t* c32 = lds + a.cap;
-  const uint32_t lo = a.row_ptr[r], hi = a.row_ptr[r + 1];
-  __syncthreads();  // the previous root's counts are read no more
-  for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) {
-    minw[i] = kInf;
-    c32[i] = 0;
-  }
-  __syncthreads();
-  if (!a.hop) {
-    for (uint32_t e = lo + threadIdx.x; e < hi; e += blockDim.x) {
-      const uint32_t d = a.didx[e];
-      if (!(a.colx[e] & 0x80000000u) && d < ns) atomicMin(&minw[d], a.w[e]);
-    }
-    __syncthreads();
-  }
-  for (uint32_t e = lo + threadIdx.x; e < hi; e += blockDim.x) {
-    const uint32_t d = a.didx[e];
-    if ((a.colx[e] & 0x80000000u) || d >= ns) continue;
-    if (a.hop || a.w[e] == minw[d]) atomicAdd(&c32[d], 1u);
-  }
-  __syncthreads();
-  // pack slot i's count into half i of the minw words (dead by now; the u32
-  // counts lie behind them and are not overwritten)
-  uint16_t* c16 = reinterpret_cast<uint16_t*>(lds);
-  for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) c16[i] = (uint16_t)min(c32[i], 0xFFFFu);
-  __syncthreads();
-}
 
 __global__ __launch_bounds__(256) void policy_kernel(const PolicyArgs a) {
   extern __shared__ uint32_t lds[];
@@ -170,8 +137,14 @@ uint32_t max_row_words(const ospf_sweep* s) {
   return mw;
 }
 
+bool any_out(const ospf_select_pout* o) {
+  return o->metric || o->count || o->nh || o->links || o->need || o->best;
+}
+
+}  // namespace
+
 // the policy table's contract beyond ospf_select_table's
-const char* ptable_error(const ospf_select_ptable* t, uint32_t V) {
+const char* ospf_int::sweep::select_ptable_check(const ospf_select_ptable* t, uint32_t V) {
   if (!t) return "select: null table";
   const ospf_select_table plain{t->n_prefixes, t->offsets, t->nodes};
   if (const char* bad = select_table_check(&plain, V)) return bad;
@@ -182,19 +155,13 @@ const char* ptable_error(const ospf_select_ptable* t, uint32_t V) {
   return nullptr;
 }
 
-bool any_out(const ospf_select_pout* o) {
-  return o->metric || o->count || o->nh || o->links || o->need || o->best;
-}
-
-}  // namespace
-
 // ospf_sweep_select_policy_dev without the fault-injection hook (the host and
 // multi-device calls hook once themselves)
 int ospf_int::sweep::policy_queue(ospf_sweep* s, const ospf_select_ptable* t, uint32_t nh_words,
                                   const ospf_select_pout* d_out, void* stream) {
   ospf_ctx* c = s->c;
   if (!s->ran) return sfail(s, OSPF_E_INVAL, "sweep: select before the first run");
-  if (const char* bad = ptable_error(t, s->V)) return sfail(s, OSPF_E_INVAL, bad);
+  if (const char* bad = select_ptable_check(t, s->V)) return sfail(s, OSPF_E_INVAL, bad);
   if (nh_words < max_row_words(s))
     return sfail(s, OSPF_E_INVAL, "sweep: nh_words below a root's next-hop words");
   // the kernel reads the live CSR and no-transit bits beside the rows

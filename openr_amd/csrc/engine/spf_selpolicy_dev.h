@@ -1,7 +1,7 @@
 // spf_selpolicy_dev.h — the per-prefix device functions of route selection
-// under the reference's best-route policy (spf_selpolicy.hip: policy_kernel;
-// written so that a resident-selection kernel such as seldelta_kernel could
-// call them too). Per (root r, prefix p) createRouteForPrefix
+// under the reference's best-route policy (spf_selpolicy.hip: policy_kernel,
+// the one-shot selection; spf_seldelta_policy.hip: seldelta_policy_kernel,
+// the resident selection and its delta). Per (root r, prefix p) createRouteForPrefix
 // (openr/decision/SpfSolver.cpp:197-458) before it takes the minimum
 //   R  = the announcers r reaches                                  (:229-244)
 //   S  = those of R in the best (path pref, source pref, distance) class
@@ -261,6 +261,41 @@ __device__ __forceinline__ uint32_t policy_by_words(const Table& t,
     policy_reduce(need, smallest, has_root, r, kmin, e);
   }
   return want_links ? wave_sum(links) : 0u;
+}
+
+// c[0 .. ns) of root r into LDS as u16 (the first ns halves of `lds`); lds
+// holds 2 * a.cap words. Block-wide, with barriers. `a`: a kernel's arguments
+// with the loaded graph's row_ptr / colx / w / didx, hop and cap (LDS slots).
+template <class Args>
+__device__ __forceinline__ void build_links(const Args& a, uint32_t r, uint32_t ns,
+                                            uint32_t* lds) {
+  uint32_t* minw = lds;
+  uint32_t* c32 = lds + a.cap;
+  const uint32_t lo = a.row_ptr[r], hi = a.row_ptr[r + 1];
+  __syncthreads();  // the previous root's counts are read no more
+  for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) {
+    minw[i] = kInf;
+    c32[i] = 0;
+  }
+  __syncthreads();
+  if (!a.hop) {
+    for (uint32_t e = lo + threadIdx.x; e < hi; e += blockDim.x) {
+      const uint32_t d = a.didx[e];
+      if (!(a.colx[e] & 0x80000000u) && d < ns) atomicMin(&minw[d], a.w[e]);
+    }
+    __syncthreads();
+  }
+  for (uint32_t e = lo + threadIdx.x; e < hi; e += blockDim.x) {
+    const uint32_t d = a.didx[e];
+    if ((a.colx[e] & 0x80000000u) || d >= ns) continue;
+    if (a.hop || a.w[e] == minw[d]) atomicAdd(&c32[d], 1u);
+  }
+  __syncthreads();
+  // pack slot i's count into half i of the minw words (dead by now; the u32
+  // counts lie behind them and are not overwritten)
+  uint16_t* c16 = reinterpret_cast<uint16_t*>(lds);
+  for (uint32_t i = threadIdx.x; i < ns; i += blockDim.x) c16[i] = (uint16_t)min(c32[i], 0xFFFFu);
+  __syncthreads();
 }
 
 // the next-hop links of an entry whose words one lane holds (W <= kSelLaneW)

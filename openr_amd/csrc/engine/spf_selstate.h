@@ -1,6 +1,7 @@
 // spf_selstate.h — the select state and what its translation units share:
-// spf_seldelta.hip (the resident selection, prime / update / copy) and
-// spf_ucmp.hip (the UCMP weights resolved over it). Not a public header.
+// spf_seldelta.hip (the resident selection, prime / update / copy),
+// spf_seldelta_policy.hip (the same under the best-route policy) and
+// spf_ucmp.hip (the UCMP weights resolved over either). Not a public header.
 #pragma once
 
 #include <algorithm>
@@ -9,6 +10,8 @@
 
 #include "spf_internal.h"
 
+struct ospf_sweep;
+
 // ---------------------------------------------------------------- the state
 struct ospf_selstate {
   ospf_ctx* c = nullptr;
@@ -16,6 +19,13 @@ struct ospf_selstate {
   uint32_t V = 0, P = 0;
   std::vector<uint32_t> t_off, t_nodes;  // the table's copy
   uint32_t* d_tab = nullptr;             // offsets, then nodes
+  // a policy state (ospf_selstate_create_policy): an entry's header is metric,
+  // count, links, need, best (hdr = 5) instead of metric, count (hdr = 2); the
+  // table's policy columns, parallel to t_nodes (t_mnh empty: all unset)
+  bool policy = false;
+  uint32_t hdr = 2;
+  std::vector<uint32_t> t_pref, t_mnh;
+  uint32_t* d_pol = nullptr;  // pref, then min_nexthop
   bool primed = false;
   int cur = 0;  // the committed buffer
   struct Buf {
@@ -31,7 +41,7 @@ struct ospf_selstate {
   } b[2];
   uint32_t* d_roots = nullptr;  // [V]
   uint32_t* d_cnt = nullptr;    // [2]
-  uint4* d_chg = nullptr;
+  uint4* d_chg = nullptr;  // change records: one uint4 each, two in a policy state
   uint32_t* d_chg_nh = nullptr;
   uint32_t* d_reb = nullptr;
   size_t chg_cap = 0, chg_nh_words = 0, reb_cap = 0;
@@ -84,6 +94,28 @@ int grow(ospf_selstate* st, T** p, size_t* have, size_t count) {
   st->device_bytes += count * sizeof(T);
   return OSPF_OK;
 }
+
+// ---- spf_seldelta.hip
+// a state over `t`; with `pol` (its offsets / nodes are t's) a policy state
+int create(ospf_ctx* c, const ospf_select_table* t, const ospf_select_ptable* pol,
+           ospf_selstate** out);
+// sw's selection into the shadow buffer; with `compare` the entries that
+// differ from the committed buffer's and the rebased roots are listed (up to
+// the caps) and counted. Nothing is committed.
+int write_shadow(ospf_selstate* st, ospf_sweep* sw, bool compare, uint32_t nh_words, bool want_nh,
+                 uint32_t cap, uint32_t cap_reb, uint32_t counts[2]);
+// what makes `sw` unusable for the state (null: usable)
+const char* sweep_error(const ospf_selstate* st, const ospf_sweep* sw);
+// the committed selection is sw's: what a consumer of the state checks it by
+void committed(ospf_selstate* st, const ospf_sweep* sw);
+// the widest owned root's next-hop words
+uint32_t max_words(const ospf_sweep* sw);
+
+// ---- spf_seldelta_policy.hip
+// write_shadow's launch for a policy state (the buffers, lists and counters
+// are in place): queued on the null stream, not waited for
+int policy_delta_launch(ospf_selstate* st, ospf_sweep* sw, bool compare, uint32_t nh_words,
+                        bool want_nh, uint32_t cap, uint32_t cap_reb);
 
 }  // namespace selst
 }  // namespace ospf_int

@@ -34,6 +34,10 @@
 // by another workgroup in the same launch reads as pending whether or not its
 // store is visible yet: the result and the round count (the hop depth of the
 // deepest selected path) do not depend on scheduling.
+// Over a policy state (spf_seldelta_policy.hip: five header columns before an
+// entry's words) an announcer need not select itself, so a selected next hop
+// whose no-transit bit is set counts with its leaf weight and is never waited
+// for (drained_leaf; DESIGN.md §3 (q''')).
 // No LDS, no scratch, no inline assembly; plain vector stores and atomics.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -91,6 +95,9 @@ __global__ __launch_bounds__(256) void ucmp_links_kernel(const LinkArgs a) {
 // ---------------------------------------------------------------- the rounds
 struct RoundArgs {
   uint32_t V, P, round, adj;
+  uint32_t hdr;     // header columns before an entry's words: 2, or 5 in a policy state
+  uint32_t policy;  // the drained-leaf rule applies (a policy state)
+  const uint32_t* nt_bits;  // the loaded graph's no-transit bitmap
   const uint32_t* data;  // the committed selection: root blocks
   const uint64_t* off;
   const uint32_t* w;
@@ -119,23 +126,59 @@ struct Acc {
   }
 };
 
+// node u's position in prefix p's sorted announcer list (the last entry <= u;
+// the prefix has announcers)
+__device__ __forceinline__ uint32_t leaf_pos(const uint32_t* t_off, const uint32_t* t_nodes,
+                                             uint32_t p, uint32_t u) {
+  uint32_t lo = t_off[p], hi = t_off[p + 1];
+  while (lo + 1 < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (t_nodes[mid] <= u) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// Under the policy a next hop k whose no-transit bit is set is a leaf of the
+// entry (nothing transits k, so k is the destination) but need not select
+// itself in its own entry: its leaf weight for p, read from the table. False
+// when the rule does not apply to k.
+__device__ __forceinline__ bool drained_leaf(const uint32_t* nt_bits, const uint32_t* t_off,
+                                             const uint32_t* t_nodes, const int64_t* leaf_w,
+                                             uint32_t k, uint32_t p, int64_t& w) {
+  if (!((nt_bits[k >> 5] >> (k & 31u)) & 1u) || t_off[p] == t_off[p + 1]) return false;
+  const uint32_t at = leaf_pos(t_off, t_nodes, p, k);
+  if (t_nodes[at] != k) return false;
+  w = leaf_w[at];
+  return true;
+}
+
 // next hop `slot` (node k) of prefix p into acc
 __device__ __forceinline__ void take_hop(const RoundArgs& a, uint32_t slot, uint32_t k, uint32_t p,
                                          Acc& acc) {
   const size_t i = (size_t)k * a.P + p;
-  const uint32_t tg = a.tag[i];
-  if (tg == kPending || (tg & kRoundMask) >= a.round) {
-    acc.wait = true;
-    return;
+  int64_t wk = 0;
+  if (a.policy && drained_leaf(a.nt_bits, a.t_off, a.t_nodes, a.leaf_w, k, p, wk)) {
+    if (wk <= 0) {  // never waited for; a zero leaf weight voids the entry
+      acc.isvoid = true;
+      return;
+    }
+  } else {
+    const uint32_t tg = a.tag[i];
+    if (tg == kPending || (tg & kRoundMask) >= a.round) {
+      acc.wait = true;
+      return;
+    }
+    const uint32_t st = tg >> 30;
+    if (st == OSPF_UCMP_VOID) acc.isvoid = true;
+    if (st == OSPF_UCMP_OVERFLOW) acc.ovf = true;
+    if (st != OSPF_UCMP_OK) return;  // (NONE cannot be a selected next hop's)
+    wk = a.W[i];
   }
-  const uint32_t st = tg >> 30;
-  if (st == OSPF_UCMP_VOID) acc.isvoid = true;
-  if (st == OSPF_UCMP_OVERFLOW) acc.ovf = true;
-  if (st != OSPF_UCMP_OK) return;  // (NONE cannot be a selected next hop's)
   if (a.adj) {
     acc.add((uint64_t)a.S[slot]);
   } else {
-    const uint64_t w = (uint64_t)a.W[i], c = a.c[slot];
+    const uint64_t w = (uint64_t)wk, c = a.c[slot];
     const uint64_t lo = w * c;
     if (__umul64hi(w, c) || lo > kI63) acc.ovf = true;
     else acc.add(lo);
@@ -151,7 +194,7 @@ __global__ __launch_bounds__(256) void ucmp_round_kernel(const RoundArgs a) {
   const uint32_t P = a.P;
   for (uint32_t u = blockIdx.x; u < a.V; u += gridDim.x) {
     const uint32_t* __restrict__ m_ = a.data + a.off[u];
-    const uint32_t* __restrict__ nh = m_ + 2 * (size_t)P;
+    const uint32_t* __restrict__ nh = m_ + a.hdr * (size_t)P;
     const uint32_t W = a.w[u];
     const uint32_t s0 = a.dn_off[u], ns = a.dn_off[u + 1] - s0;
     int64_t* Wu = a.W + (size_t)u * P;
@@ -168,13 +211,7 @@ __global__ __launch_bounds__(256) void ucmp_round_kernel(const RoundArgs a) {
           if (m == kInf) {
             tg = make_tag(OSPF_UCMP_NONE, 0);
           } else if (m == 0) {  // u announces: its position in the prefix's sorted list
-            uint32_t lo = a.t_off[p], hi = a.t_off[p + 1];
-            while (lo + 1 < hi) {
-              const uint32_t mid = (lo + hi) >> 1;
-              if (a.t_nodes[mid] <= u) lo = mid;
-              else hi = mid;
-            }
-            w = a.leaf_w[lo];
+            w = a.leaf_w[leaf_pos(a.t_off, a.t_nodes, p, u)];
             tg = make_tag(w > 0 ? OSPF_UCMP_OK : OSPF_UCMP_VOID, 0);
           }
           Wu[p] = w;
@@ -236,6 +273,11 @@ __global__ __launch_bounds__(256) void ucmp_round_kernel(const RoundArgs a) {
 // ---------------------------------------------------------------- the view
 struct ViewArgs {
   uint32_t n, P, fill;  // 0: count the weights of each entry; 1: write; 2: write, no weights
+  uint32_t hdr, policy;  // as RoundArgs
+  const uint32_t* nt_bits;
+  const uint32_t* t_off;
+  const uint32_t* t_nodes;
+  const int64_t* leaf_w;
   const uint32_t* roots;
   const uint32_t* data;
   const uint64_t* off;
@@ -260,13 +302,20 @@ __device__ __forceinline__ uint64_t gcd64(uint64_t x, uint64_t y) {
   return x;
 }
 
+// the weight next hop k of prefix p carries in a root's link view
+__device__ __forceinline__ uint64_t hop_weight(const ViewArgs& a, uint32_t k, uint32_t p) {
+  int64_t w;
+  if (a.policy && drained_leaf(a.nt_bits, a.t_off, a.t_nodes, a.leaf_w, k, p, w)) return (uint64_t)w;
+  return (uint64_t)a.W[(size_t)k * a.P + p];
+}
+
 // A thread per (root, prefix), lane = prefix: the entry's next-hop words twice
 // (gcd, then the quotients), the gathers W[k][p] coalesced as in the rounds.
 __global__ __launch_bounds__(256) void ucmp_view_kernel(const ViewArgs a) {
   const uint32_t P = a.P;
   for (uint32_t i = blockIdx.x; i < a.n; i += gridDim.x) {
     const uint32_t r = a.roots[i];
-    const uint32_t* nh = a.data + a.off[r] + 2 * (size_t)P;
+    const uint32_t* nh = a.data + a.off[r] + a.hdr * (size_t)P;
     const uint32_t W = a.w[r];
     const uint32_t s0 = a.dn_off[r], ns = a.dn_off[r + 1] - s0;
     for (uint32_t p = threadIdx.x; p < P; p += blockDim.x) {
@@ -291,14 +340,14 @@ __global__ __launch_bounds__(256) void ucmp_view_kernel(const ViewArgs a) {
       for (uint32_t x = 0; x < W; ++x)
         for (uint32_t bits = wd[x]; bits; bits &= bits - 1u) {
           const uint32_t b = 32u * x + (uint32_t)__ffs((int)bits) - 1u;
-          if (b < ns) g = gcd64(g, (uint64_t)a.W[(size_t)a.dn[s0 + b] * P + p]);
+          if (b < ns) g = gcd64(g, hop_weight(a, a.dn[s0 + b], p));
         }
       int64_t* out = a.o_wt + a.o_off[e];
       for (uint32_t x = 0; x < W; ++x)
         for (uint32_t bits = wd[x]; bits; bits &= bits - 1u) {
           const uint32_t b = 32u * x + (uint32_t)__ffs((int)bits) - 1u;
           if (b >= ns) continue;
-          const uint64_t w = (uint64_t)a.W[(size_t)a.dn[s0 + b] * P + p];
+          const uint64_t w = hop_weight(a, a.dn[s0 + b], p);
           *out++ = (int64_t)(g > 1 ? w / g : w);
         }
     }
@@ -436,6 +485,9 @@ int ospf_selstate_ucmp(ospf_selstate* st, uint32_t algo, const int64_t* leaf_wei
   a.V = V;
   a.P = P;
   a.adj = adj ? 1u : 0u;
+  a.hdr = st->hdr;
+  a.policy = st->policy ? 1u : 0u;
+  a.nt_bits = c->g.nt_bits;
   a.data = b.data;
   a.off = b.off;
   a.w = b.w;
@@ -511,6 +563,12 @@ int ospf_selstate_ucmp_copy(ospf_selstate* st, const uint32_t* roots, uint32_t n
   ViewArgs a{};
   a.n = n;
   a.P = (uint32_t)P;
+  a.hdr = st->hdr;
+  a.policy = st->policy ? 1u : 0u;
+  a.nt_bits = c->g.nt_bits;
+  a.t_off = st->d_tab;
+  a.t_nodes = st->d_tab + P + 1;
+  a.leaf_w = u->leaf_w;
   a.roots = d_roots.as<uint32_t>();
   a.data = b.data;
   a.off = b.off;

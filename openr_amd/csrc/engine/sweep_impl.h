@@ -280,6 +280,9 @@ struct SelectOut {
 // multi-device calls hook once themselves)
 int policy_queue(ospf_sweep* s, const ospf_select_ptable* t, uint32_t nh_words,
                  const ospf_select_pout* d_out, void* stream);
+// the policy table's contract (ospf_select_ptable) for a graph of V nodes:
+// null when it holds, else what is wrong
+const char* select_ptable_check(const ospf_select_ptable* t, uint32_t V);
 
 // device outputs of one policy select (only the wanted ones of `want`), freed
 // by the destructor

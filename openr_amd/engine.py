@@ -76,6 +76,9 @@ def _policy_host_out(n: int, P: int, W: int, want: Sequence[str]):
 # ospf_select_change / odl_select_change records
 CHANGE_DTYPE = np.dtype([("root", np.uint32), ("prefix", np.uint32), ("metric", np.uint32),
                          ("count", np.uint32)])
+# ospf_select_pchange records
+PCHANGE_DTYPE = np.dtype([(k, np.uint32) for k in ("root", "prefix", "metric", "count", "links",
+                                                   "need", "best", "installed")])
 
 
 def decode_paths(recs: np.ndarray, status: np.ndarray, bad: int):
@@ -535,17 +538,28 @@ class SelState:
     """ospf_selstate: the selection of one prefix table for every root, kept
     on the device in each root's own width, and the entries a later sweep
     changed (DecisionRouteDb::calculateUpdate for ospf_sweep_select's route
-    DB). Bound to an Engine (not to a Sweep) and to one table."""
+    DB). Bound to an Engine (not to a Sweep) and to one table. With `pref`
+    (a class rank per announcer entry; optionally `min_nexthop`) a policy
+    state: it holds Sweep.select_policy's selection and is driven by
+    update_policy / copy_policy / set_policy instead of update."""
 
-    def __init__(self, engine: "Engine", offsets: Sequence[int], nodes: Sequence[int]):
+    def __init__(self, engine: "Engine", offsets: Sequence[int], nodes: Sequence[int],
+                 pref: Optional[Sequence[int]] = None,
+                 min_nexthop: Optional[Sequence[int]] = None):
         self._L = N.engine()
         self.engine = engine
-        t, keep = select_table(offsets, nodes)
-        self.P = int(t.n_prefixes)
+        self.policy = pref is not None or min_nexthop is not None
         h = C.c_void_p()
-        rc = self._L.ospf_selstate_create(engine._h, C.byref(t), C.byref(h))
+        if self.policy:
+            t, keep = select_ptable(offsets, nodes, pref, min_nexthop)
+            rc = self._L.ospf_selstate_create_policy(engine._h, C.byref(t), C.byref(h))
+        else:
+            t, keep = select_table(offsets, nodes)
+            rc = self._L.ospf_selstate_create(engine._h, C.byref(t), C.byref(h))
         if rc != 0:
             raise EngineError(rc, self._L.ospf_last_error(engine._h).decode())
+        self.P = int(t.n_prefixes)
+        self.n_entries = int(keep[1].size)
         self._h = h
 
     def close(self):
@@ -606,6 +620,58 @@ class SelState:
             raise EngineError(rc, self._msg())
         return metric, count, nh
 
+    # ------------------------------------------------------------ policy
+    def update_policy(self, sweep: "Sweep", cap: int = 1024, cap_rebased: int = 64,
+                      nh_words: int = 0, want_nh: bool = True):
+        """ospf_selstate_update_policy: update() for a policy state -> (changes
+        [n] structured u32 root / prefix / metric / count / links / need / best
+        / installed with the NEW values, nh [n, W] u32 or None, rebased roots
+        [m] u32). Raises SelStateOverflow as update() does."""
+        if cap < 0 or cap_rebased < 0 or nh_words < 0:
+            raise ValueError("capacities and nh_words must be >= 0")
+        W = nh_words or max(1, sweep.max_nh_words)
+        rec = np.zeros(max(1, cap), PCHANGE_DTYPE)
+        nh = np.zeros((max(1, cap), W), np.uint32) if want_nh else None
+        reb = np.zeros(max(1, cap_rebased), np.uint32)
+        n, m = C.c_uint32(), C.c_uint32()
+        rc = self._L.ospf_selstate_update_policy(self._h, sweep._h, W, rec.ctypes.data,
+                                                 nh.ctypes.data if want_nh else None, cap,
+                                                 C.byref(n), reb.ctypes.data, cap_rebased,
+                                                 C.byref(m))
+        if rc == -4:
+            raise SelStateOverflow(self._msg(), int(n.value), int(m.value))
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+        return rec[: n.value], (nh[: n.value] if want_nh else None), reb[: m.value]
+
+    def copy_policy(self, roots: Sequence[int], nh_words: int,
+                    want: Sequence[str] = POLICY_OUTPUTS) -> Dict[str, np.ndarray]:
+        """ospf_selstate_copy_policy: the committed entries of `roots` (node
+        ids) in Sweep.select_policy's layout; only the outputs in `want`."""
+        roots = np.ascontiguousarray(roots, np.uint32)
+        if nh_words < 1:
+            raise ValueError("nh_words must be >= 1")
+        o, arrs = _policy_host_out(roots.size, self.P, nh_words, want)
+        rc = self._L.ospf_selstate_copy_policy(self._h, roots.ctypes.data, roots.size, nh_words,
+                                               C.byref(o))
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+        return arrs
+
+    def set_policy(self, pref: Optional[Sequence[int]],
+                   min_nexthop: Optional[Sequence[int]] = None) -> None:
+        """ospf_selstate_set_policy: replace the class ranks and thresholds
+        (one per announcer entry). Nothing committed changes; the next
+        update_policy reports what the new attributes changed."""
+        pr = None if pref is None else np.ascontiguousarray(pref, np.uint32)
+        mn = None if min_nexthop is None else np.ascontiguousarray(min_nexthop, np.uint32)
+        for a in (pr, mn):
+            if a is not None and a.size != self.n_entries:
+                raise ValueError("pref / min_nexthop: one per announcer entry")
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        rc = self._L.ospf_selstate_set_policy(self._h, ptr(pr), ptr(mn))
+        if rc != 0:
+            raise EngineError(rc, self._msg())
 
     # ------------------------------------------------------------ UCMP
     @property

@@ -576,16 +576,8 @@ class LinkState:
         a dict by node id (node_names() order), columns in the dict's order:
         metric / count / links / need / best [V, P] u32, nh [V, P, W] u32 and
         installed [V, P] bool (links > 0 and need <= links)."""
-        unset = -(1 << 63)
-        lines, attrs = [], []
-        for ann in prefixes.values():
-            for nm, pp, sp, dist, mn in ann:
-                if not nm or "\n" in nm or "\t" in nm:
-                    raise ValueError("node names must be non-empty, without tabs and newlines")
-                attrs.append((int(pp), int(sp), int(dist), unset if mn is None else int(mn)))
-            lines.append("\t".join(a[0] for a in ann))
+        lines, at = self._policy_lines(prefixes)
         txt = "\n".join(lines).encode()
-        at = np.ascontiguousarray(attrs, np.int64).reshape(-1, 4)
         args = (self._h, txt, len(lines), at.ctypes.data if at.size else None, at.shape[0],
                 int(use_link_metric))
         need = C.c_uint32(0)
@@ -600,6 +592,91 @@ class LinkState:
                 *args, W, None, out["metric"].ctypes.data, out["count"].ctypes.data,
                 out["nh"].ctypes.data, out["links"].ctypes.data, out["need"].ctypes.data,
                 out["best"].ctypes.data, inst.ctypes.data) != 0:
+            raise LinkStateError(self._err())
+        out["installed"] = inst.astype(bool)
+        return out
+
+    @staticmethod
+    def _policy_lines(prefixes: Dict[str, Sequence[tuple]]):
+        """{prefix: [(name, path_pref, source_pref, distance, min_nexthop_or_None)]}
+        -> (tab-separated name lines, attribute sets [n, 4] i64)"""
+        unset = -(1 << 63)
+        lines, attrs = [], []
+        for ann in prefixes.values():
+            for nm, pp, sp, dist, mn in ann:
+                if not nm or "\n" in nm or "\t" in nm:
+                    raise ValueError("node names must be non-empty, without tabs and newlines")
+                attrs.append((int(pp), int(sp), int(dist), unset if mn is None else int(mn)))
+            lines.append("\t".join(a[0] for a in ann))
+        return lines, np.ascontiguousarray(attrs, np.int64).reshape(-1, 4)
+
+    def track_select_policy(self, prefixes: Dict[str, Sequence[tuple]],
+                            use_link_metric: bool = True) -> None:
+        """odl_track_select_policy: bind the LinkState to a prefix table with
+        attributes (all_sources_select_policy's form) and store the policy
+        selection as the baseline of policy_delta, on the device."""
+        lines, at = self._policy_lines(prefixes)
+        if self._L.odl_track_select_policy(self._h, "\n".join(lines).encode(), len(lines),
+                                           at.ctypes.data if at.size else None, at.shape[0],
+                                           int(use_link_metric)) != 0:
+            raise LinkStateError(self._err())
+        self._tracked_prefixes = len(lines)
+
+    def set_tracked_policy(self, prefixes: Dict[str, Sequence[tuple]]) -> None:
+        """odl_set_tracked_attrs: new attributes for the tracked table (the
+        same announcer names per prefix, in track_select_policy's order); the
+        next policy_delta reports what they changed."""
+        _, at = self._policy_lines(prefixes)
+        if self._L.odl_set_tracked_attrs(self._h, at.ctypes.data if at.size else None,
+                                         at.shape[0]) != 0:
+            raise LinkStateError(self._err())
+
+    def policy_delta(self) -> dict:
+        """odl_policy_delta: select_delta over the policy selection -> dict(
+        changes = structured array root / prefix / metric / count / links /
+        need / best / installed with the NEW values, nh [n, W] u32, rebased
+        node ids, full)."""
+        n, m, W, full = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_int32()
+        pc, pn, pr = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        if self._L.odl_policy_delta(self._h, C.byref(n), C.byref(m), C.byref(W), C.byref(full),
+                                    C.byref(pc), C.byref(pn), C.byref(pr)) != 0:
+            raise LinkStateError(self._err())
+        try:
+            def take(p, count, dtype):
+                if not count:
+                    return np.zeros(0, dtype)
+                nbytes = count * np.dtype(dtype).itemsize
+                return np.frombuffer(C.string_at(p, nbytes), dtype).copy()
+            from .engine import PCHANGE_DTYPE
+            changes = take(pc, n.value, PCHANGE_DTYPE)
+            nh = take(pn, n.value * W.value, np.uint32).reshape(n.value, W.value)
+            rebased = take(pr, m.value, np.uint32)
+        finally:
+            for p in (pc, pn, pr):
+                self._L.odl_free_buf(p)
+        return {"changes": changes, "nh": nh, "rebased": rebased, "full": bool(full.value)}
+
+    def policy_tracked(self, nodes: Sequence[str], nh_words: int = 0) -> dict:
+        """odl_policy_tracked: the baseline of some nodes (names) in
+        all_sources_select_policy's layout (rows = nodes)."""
+        if not hasattr(self, "_tracked_prefixes"):
+            raise LinkStateError("policy_tracked: no tracked table (track_select_policy)")
+        P, W = self._tracked_prefixes, nh_words
+        if not W:
+            need = C.c_uint32(0)
+            if self._L.odl_all_sources_select(self._h, b"", 0, 1, 0, C.byref(need), None, None,
+                                              None) != 0:
+                raise LinkStateError(self._err())
+            W = int(need.value)
+        n = len(nodes)
+        out = {k: np.zeros((n, P), np.uint32) for k in ("metric", "count", "links", "need", "best")}
+        out["nh"] = np.zeros((n, P, W), np.uint32)
+        inst = np.zeros((n, P), np.uint8)
+        if self._L.odl_policy_tracked(self._h, "\n".join(nodes).encode(), n, W,
+                                      out["metric"].ctypes.data, out["count"].ctypes.data,
+                                      out["nh"].ctypes.data, out["links"].ctypes.data,
+                                      out["need"].ctypes.data, out["best"].ctypes.data,
+                                      inst.ctypes.data) != 0:
             raise LinkStateError(self._err())
         out["installed"] = inst.astype(bool)
         return out

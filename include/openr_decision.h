@@ -215,13 +215,42 @@ int odl_all_sources_select(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefi
  *                              announcer is reached;
  *   installed [V][n_prefixes]  (bytes) 1 iff links > 0 and need <= links.
  * nh_words / *nh_words_needed as above. Not covered: SR_MPLS per-destination
- * next hops, KSP2 and per-area distance selection, BGP metric vectors,
- * several areas. */
+ * next hops, KSP2 and per-area distance selection, BGP metric vectors.
+ * Several areas: odl_areas_select_policy. */
 int odl_all_sources_select_policy(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefixes,
                                   const int64_t* attrs, uint32_t n_attrs, int use_link_metric,
                                   uint32_t nh_words, uint32_t* nh_words_needed, uint32_t* metric,
                                   uint32_t* count, uint32_t* nh, uint32_t* links, uint32_t* need,
                                   uint32_t* best, uint8_t* installed);
+/* The same selection across several areas, one LinkState each
+ * (LinkState::allAreasSelect -> ospf_areas_select_policy over the areas'
+ * resident sweeps, or the same steps on the host over each area's
+ * getSpfResult when an area is in host mode, multi-device, on another device
+ * or degraded, or when the engine call fails; a device error degrades every
+ * area, any other refusal sends only this call to the host). A line of
+ * prefixes_nl holds
+ * tab-separated fields in pairs, node name then area name; attrs as above,
+ * four int64 per pair. An unknown area is an error; a node unknown to its
+ * area is dropped with its attributes. The areas are ordered by area name:
+ * order[i] is the index into `areas` of the i-th by name, and nh_words[i],
+ * nh[i] and bit i of `areas_mask` belong to it. The union of the node names,
+ * by name bytes, gives the global ids. Need query, then fill: with
+ * names_nl NULL the call only writes *n_global, order [n_areas] and nh_words
+ * [n_areas]; otherwise *names_nl receives the global names, newline-separated
+ * (odl_free), and the outputs that are not NULL are filled: metric / count /
+ * links / need / best / areas_mask [G][n_prefixes] u32 by global id (best: the
+ * entry's position among the kept entries of its prefix in (node, area)
+ * order), installed [G][n_prefixes] bytes, nh[i] [V_i][n_prefixes]
+ * [nh_words[i]] by that area's node id. *on_device: 1 when the device
+ * answered. Errors (-1) are reported on areas[0]. Not covered: a resident
+ * multi-area state and its delta, UCMP across areas, SR_MPLS per-destination
+ * next hops and KSP2, BGP metric vectors, several devices. */
+int odl_areas_select_policy(odl_ls* const* areas, uint32_t n_areas, const char* prefixes_nl,
+                            uint32_t n_prefixes, const int64_t* attrs, uint32_t n_attrs,
+                            int use_link_metric, uint32_t* n_global, uint32_t* order,
+                            uint32_t* nh_words, char** names_nl, uint32_t* metric, uint32_t* count,
+                            uint32_t* links, uint32_t* need, uint32_t* best, uint32_t* areas_mask,
+                            uint32_t* const* nh, uint8_t* installed, int* on_device);
 /* Only the selections a topology change altered (LinkState::trackSelect /
  * selectDelta / selectTracked): DecisionRouteDb::calculateUpdate
  * (SpfSolver.cpp:24-59) for odl_all_sources_select's route DB.

@@ -705,7 +705,8 @@ int ospf_sweep_select(ospf_sweep* sw, const ospf_select_table* table, uint32_t n
  * (with announcers) and a sweep that does not describe the context's current
  * graph (the kernel reads the live CSR and no-transit bits).
  * Not covered: SR_MPLS per-destination next hops, K_SHORTEST_DISTANCE_2 and
- * PER_AREA_SHORTEST_DISTANCE, BGP metric vectors, several areas. (The same
+ * PER_AREA_SHORTEST_DISTANCE, BGP metric vectors. (Several areas:
+ * ospf_areas_select_policy below. The same
  * selection kept resident, its delta and UCMP over it: the policy state of
  * ospf_selstate_create_policy below.) */
 typedef struct ospf_select_ptable { /* host memory */
@@ -724,6 +725,88 @@ int ospf_sweep_select_policy_dev(ospf_sweep* sw, const ospf_select_ptable* table
 /* host outputs, synchronous (after the work queued on every stream) */
 int ospf_sweep_select_policy(ospf_sweep* sw, const ospf_select_ptable* table, uint32_t nh_words,
                              const ospf_select_pout* out);
+/* The same selection across several areas (createRouteForPrefix is multi-area
+ * at its core, SpfSolver.cpp:229-244, :365-443), for every node of the union
+ * of the areas and every prefix, in one launch. Areas 0 .. n_areas - 1 are
+ * given in area-name byte order; each is one sweep that has run, owns every
+ * root (one part) and describes its context's current graph, all on one
+ * device and in one metric mode. The union of the node names, sorted by name
+ * bytes, gives global ids 0 .. n_global - 1; gid[a][i] is the global id of
+ * area a's node i (strictly ascending in i: both orders are name rank). An
+ * entry of a prefix is a (global node n, area a) pair with pref (< 2^31,
+ * smaller wins) and min_nexthop (0 = unset); entries are strictly ascending
+ * per prefix in (n, a) -- the order of the reference's std::set<NodeAndArea>,
+ * which decides bestNodeArea -- and n exists in a. Per global root g (its
+ * areas: those that contain it) and prefix p:
+ *   R  = the entries (n, a) with g in a and dist_a[g][n] finite (reachability
+ *        is judged in the entry's own area only; g itself is at distance 0);
+ *   S  = the entries of R at the smallest pref;
+ *   S' = the entries of S whose node is not drained in its own area's loaded
+ *        graph, or S when all are (:709-731);
+ *   per area a of g with at least one entry OF ITS OWN in S' (the default
+ *   computation rules): the destinations are the nodes of ALL of S', whatever
+ *   their area, that exist in a and that g reaches there (the reference looks
+ *   other areas' announcers up in this area's SPF, :805-806, :1064-1068);
+ *   m_a = the smallest dist_a[g][.] over them, L_a = those at m_a (each node
+ *   once), nh_a = the OR of their next-hop words in a;
+ *   metric = the smallest m_a; the winning areas are those at it (:399-407).
+ * Outputs, by global id:
+ *   metric [G][P]  OSPF_DIST_INF when R is empty;
+ *   count  [G][P]  the sum of |L_a| over the winning areas;
+ *   links  [G][P]  the sum over the winning areas of the links of nh_a, c(r, k)
+ *                  from that area's loaded graph as ospf_sweep_select_policy
+ *                  has it (next hops of different areas never merge: the area
+ *                  is part of the next hop);
+ *   need   [G][P]  the largest min_nexthop over S', all areas; the route is
+ *                  withheld iff need > links and links > 0;
+ *   best   [G][P]  the position within the prefix of the first entry of S
+ *                  whose node is g, else of the first entry of S (S, not S');
+ *                  0xFFFFFFFF when R is empty;
+ *   areas  [G][P]  the bit mask of the winning areas (0 when R is empty);
+ *   nh[a]  [V_a][P][nh_words[a]]  by area a's node id: nh_a of a winning area,
+ *                  zero for any other; nh_words[a] >= that sweep's max_nh_words.
+ * With one area this is ospf_sweep_select_policy word for word, rows by node
+ * id and best as an entry position. Any output may be NULL (`nh` as a whole or
+ * one area's); every word of a wanted output is written exactly once by plain
+ * stores; nothing is written on error. The _dev call uploads the table, the
+ * global -> local id maps and the per-area pointers, then queues the kernel on
+ * `stream` (a stream of area 0's device); it does not wait for other streams.
+ * The upload is one synchronous copy from host memory, into a block kept on
+ * area 0's sweep: the call first waits on the host for the kernel of the
+ * previous areas call made through that sweep, so two such calls do not
+ * overlap.
+ * OSPF_E_INVAL with the reason in area 0's sweep's last error: n_areas 0 or
+ * > 32, a NULL sweep, sweeps on different devices, a sweep that has not run,
+ * is stale against its context's graph or does not own every root, mixed
+ * metric modes, gid not strictly ascending or >= n_global, a global id no area
+ * holds, an entry whose node is absent from its area, entries not strictly
+ * ascending in (node, area), area >= n_areas, pref >= 2^31 or NULL with
+ * entries, an nh_words[a] too small. n_prefixes == 0: OSPF_OK, nothing written.
+ * Not covered: a resident multi-area state and its delta, UCMP across areas,
+ * SR_MPLS per-destination next hops and KSP2, BGP metric vectors, ospf_msweep
+ * and several devices. */
+typedef struct ospf_areas_table { /* host memory */
+  uint32_t n_areas;               /* 1 .. 32 */
+  ospf_sweep* const* sweeps;      /* [n_areas] */
+  const uint32_t* const* gid;     /* [n_areas][V_a] */
+  uint32_t n_global;
+  uint32_t n_prefixes;
+  const uint32_t* offsets;        /* [n_prefixes + 1] */
+  const uint32_t* node;           /* [offsets[P]] global ids */
+  const uint32_t* area;           /* [offsets[P]] */
+  const uint32_t* pref;           /* [offsets[P]], < 2^31, smaller wins */
+  const uint32_t* min_nexthop;    /* [offsets[P]] or NULL (all unset) */
+} ospf_areas_table;
+typedef struct ospf_areas_pout {
+  uint32_t *metric, *count, *links, *need, *best, *areas; /* [G][P] */
+  uint32_t* const* nh;            /* [n_areas] (an entry may be NULL), or NULL */
+  const uint32_t* nh_words;       /* [n_areas]; may be NULL when nh is */
+} ospf_areas_pout;
+/* device outputs, queued on `stream` after the uploads */
+int ospf_areas_select_policy_dev(const ospf_areas_table* table, const ospf_areas_pout* d_out,
+                                 void* stream);
+/* host outputs, synchronous (after the work queued on every stream) */
+int ospf_areas_select_policy(const ospf_areas_table* table, const ospf_areas_pout* out);
 /* Only the route selections a re-sweep changed: the counterpart of
  * DecisionRouteDb::calculateUpdate (openr/decision/SpfSolver.cpp:24-59, called
  * from Decision.cpp:963) for the route DB ospf_sweep_select answers. An

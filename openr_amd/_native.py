@@ -42,6 +42,7 @@ ENGINE_SYMBOLS = [
     "ospf_sweep_row", "ospf_sweep_copy_rows", "ospf_sweep_profile", "ospf_sweep_graph_memsets",
     "ospf_sweep_select_dev", "ospf_sweep_select", "ospf_msweep_select",
     "ospf_sweep_select_policy_dev", "ospf_sweep_select_policy", "ospf_msweep_select_policy",
+    "ospf_areas_select_policy_dev", "ospf_areas_select_policy",
     "ospf_selstate_create", "ospf_selstate_destroy", "ospf_selstate_last_error",
     "ospf_selstate_device_bytes", "ospf_selstate_prime", "ospf_selstate_update", "ospf_selstate_copy",
     "ospf_selstate_ucmp", "ospf_selstate_ucmp_copy", "ospf_selstate_ucmp_info",
@@ -61,6 +62,7 @@ DECISION_SYMBOLS = [
     "odl_apply_kvs", "odl_apply_publication", "odl_node_patches", "odl_shard_stats", "odl_route_db_multi_text", "odl_adjdbs_decode", "odl_adjdbs_stream", "odl_adjdbs_error", "odl_adjdbs_free",
     "odl_last_decode_error", "odl_get_counters", "odl_last_engine_error", "odl_inject_engine_error",
     "odl_set_degrade", "odl_all_sources_select", "odl_all_sources_select_policy",
+    "odl_areas_select_policy",
     "odl_track_select", "odl_select_delta", "odl_select_tracked",
     "odl_track_select_policy", "odl_policy_delta", "odl_policy_tracked", "odl_set_tracked_attrs",
     "odl_all_sources_ucmp", "odl_ucmp_tracked", "odl_ucmp_host_loop",
@@ -147,6 +149,17 @@ class ospf_select_ptable(C.Structure):  # noqa: N801
 class ospf_select_pout(C.Structure):  # noqa: N801
     _fields_ = [("metric", vp), ("count", vp), ("nh", vp), ("links", vp), ("need", vp),
                 ("best", vp)]
+
+
+class ospf_areas_table(C.Structure):  # noqa: N801
+    _fields_ = [("n_areas", u32), ("sweeps", vp), ("gid", vp), ("n_global", u32),
+                ("n_prefixes", u32), ("offsets", vp), ("node", vp), ("area", vp), ("pref", vp),
+                ("min_nexthop", vp)]
+
+
+class ospf_areas_pout(C.Structure):  # noqa: N801
+    _fields_ = [("metric", vp), ("count", vp), ("links", vp), ("need", vp), ("best", vp),
+                ("areas", vp), ("nh", vp), ("nh_words", vp)]
 
 
 class odl_counters(C.Structure):  # noqa: N801
@@ -239,6 +252,10 @@ def engine() -> C.CDLL:
                                                C.POINTER(ospf_select_pout)]
         L.ospf_msweep_select_policy.argtypes = [vp, C.POINTER(ospf_select_ptable), u32,
                                                 C.POINTER(ospf_select_pout)]
+        L.ospf_areas_select_policy_dev.argtypes = [C.POINTER(ospf_areas_table),
+                                                   C.POINTER(ospf_areas_pout), vp]
+        L.ospf_areas_select_policy.argtypes = [C.POINTER(ospf_areas_table),
+                                               C.POINTER(ospf_areas_pout)]
         L.ospf_selstate_create.argtypes = [vp, C.POINTER(ospf_select_table), C.POINTER(vp)]
         L.ospf_selstate_destroy.argtypes = [vp]
         L.ospf_selstate_last_error.argtypes = [vp]
@@ -299,6 +316,7 @@ def decision() -> C.CDLL:
         L.odl_select_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
                                        C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.odl_select_tracked.argtypes = [vp, cp, u32, u32, vp, vp, vp]
+        L.odl_areas_select_policy.argtypes = [vp, u32, cp, u32, vp, u32, i32] + [vp] * 13
         L.odl_track_select_policy.argtypes = [vp, cp, u32, vp, u32, i32]
         L.odl_policy_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
                                        C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]

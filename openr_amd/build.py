@@ -26,7 +26,8 @@ ENGINE_SRC = [os.path.join(PKG, "csrc", "engine", f)
                         "spf_probe.hip", "spf_engine.hip",
                         "spf_sweep.hip", "sweep_units.hip", "sweep_plan_derive.hip",
                         "sweep_plan_weighted.hip", "spf_multi.hip", "spf_select.hip", "spf_seldelta.hip",
-                        "spf_ucmp.hip", "spf_selpolicy.hip", "spf_seldelta_policy.hip")]
+                        "spf_ucmp.hip", "spf_selpolicy.hip", "spf_seldelta_policy.hip",
+                        "spf_selareas.hip")]
 DECISION_SRC = [os.path.join(PKG, "csrc", "decision", f)
                 for f in ("link_state.cpp", "spf_solver.cpp", "adjdb_thrift.cpp", "decision_capi.cpp")]
 ENGINE_SO = os.path.join(LIB, "libopenr_spf_hip.so")

@@ -572,6 +572,81 @@ int odl_all_sources_select_policy(odl_ls* h, const char* prefixes_nl, uint32_t n
   }, -1);
 }
 
+int odl_areas_select_policy(odl_ls* const* areas, uint32_t n_areas, const char* prefixes_nl,
+                            uint32_t n_prefixes, const int64_t* attrs, uint32_t n_attrs,
+                            int use_link_metric, uint32_t* n_global, uint32_t* order,
+                            uint32_t* nh_words, char** names_nl, uint32_t* metric, uint32_t* count,
+                            uint32_t* links, uint32_t* need, uint32_t* best, uint32_t* areas_mask,
+                            uint32_t* const* nh, uint8_t* installed, int* on_device) {
+  if (!areas || n_areas == 0 || !areas[0]) return -1;
+  return guard(areas[0], [&]() -> int {
+    std::vector<odl::LinkState*> ls;
+    for (uint32_t i = 0; i < n_areas; ++i) {
+      if (!areas[i]) throw std::invalid_argument("null area handle");
+      ls.push_back(&areas[i]->ls);
+    }
+    if (names_nl) *names_nl = nullptr;
+    if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
+    if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
+    std::vector<std::vector<odl::LinkState::AreaEntry>> prefixes;
+    size_t used = 0;
+    // the need query reads no table
+    if (names_nl)
+      for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
+        std::vector<std::string> f;
+        for (size_t b = 0; b <= ln.size();) {  // tab-separated pairs
+          size_t e = ln.find('\t', b);
+          if (e == std::string::npos) e = ln.size();
+          if (e > b || b < ln.size()) f.emplace_back(ln, b, e - b);
+          b = e + 1;
+        }
+        if (f.size() % 2) throw std::invalid_argument("prefix line: node and area names in pairs");
+        std::vector<odl::LinkState::AreaEntry> es;
+        for (size_t i = 0; i < f.size(); i += 2) {
+          if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than entries");
+          const int64_t* a = attrs + 4 * used++;
+          odl::LinkState::AreaEntry e;
+          e.node = f[i];
+          e.area = f[i + 1];
+          e.attr.pathPreference = a[0];
+          e.attr.sourcePreference = a[1];
+          e.attr.distance = a[2];
+          if (a[3] != std::numeric_limits<int64_t>::min()) e.attr.minNexthop = a[3];
+          es.push_back(std::move(e));
+        }
+        prefixes.push_back(std::move(es));
+      }
+    if (names_nl && used != n_attrs) throw std::invalid_argument("more attribute sets than entries");
+    const auto r = odl::LinkState::allAreasSelect(ls, prefixes, use_link_metric != 0);
+    if (n_global) *n_global = (uint32_t)r.names.size();
+    if (order) std::copy(r.order.begin(), r.order.end(), order);
+    if (nh_words) std::copy(r.words.begin(), r.words.end(), nh_words);
+    if (on_device) *on_device = r.onDevice ? 1 : 0;
+    if (!names_nl) return 0;
+    auto give = [](const std::vector<uint32_t>& src, uint32_t* dst) {
+      if (dst) std::copy(src.begin(), src.end(), dst);
+    };
+    give(r.metric, metric);
+    give(r.count, count);
+    give(r.links, links);
+    give(r.need, need);
+    give(r.best, best);
+    give(r.areas, areas_mask);
+    if (installed) std::copy(r.installed.begin(), r.installed.end(), installed);
+    if (nh)
+      for (uint32_t i = 0; i < n_areas; ++i) give(r.nh[i], nh[i]);
+    std::string txt;
+    for (const auto& nm : r.names) {
+      if (nm.find('\n') != std::string::npos)
+        throw std::invalid_argument("node name with a newline: " + nm);
+      txt += nm;
+      txt += '\n';
+    }
+    *names_nl = dup(txt);
+    return 0;
+  }, -1);
+}
+
 int odl_track_select(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes, int use_link_metric) {
   return guard(h, [&]() -> int {
     h->ls.trackSelect(prefixLines(prefixes_nl, n_prefixes), use_link_metric != 0);

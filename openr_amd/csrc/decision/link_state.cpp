@@ -1253,31 +1253,293 @@ void LinkState::policyTable(const std::vector<std::vector<std::string>>& prefixe
     ent.erase(std::unique(ent.begin(), ent.end(),
                           [](const auto& a, const auto& b) { return a.first == b.first; }),
               ent.end());
-    // the dense class rank: (pathPreference, sourcePreference) descending,
-    // distance ascending (selectRoutes(SHORTEST_DISTANCE), LsdbUtil.cpp:841-883)
-    using Cls = std::array<int64_t, 3>;
-    auto cls = [&](size_t i) {
-      const SelectAttr& a = attrs[p][i];
-      return Cls{a.pathPreference, a.sourcePreference, a.distance};
-    };
-    auto better = [](const Cls& a, const Cls& b) {
-      if (a[0] != b[0]) return a[0] > b[0];
-      if (a[1] != b[1]) return a[1] > b[1];
-      return a[2] < b[2];
-    };
-    std::vector<Cls> classes;
-    for (const auto& e : ent) classes.push_back(cls(e.second));
-    std::sort(classes.begin(), classes.end(), better);
-    classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
-    for (const auto& e : ent) {
-      ann[p].push_back(e.first);
-      pref[p].push_back((uint32_t)(std::lower_bound(classes.begin(), classes.end(), cls(e.second), better) -
-                                   classes.begin()));
-      const auto& mn = attrs[p][e.second].minNexthop;
-      const int64_t v = mn ? std::clamp<int64_t>(*mn, 0, 0xFFFFFFFFll) : 0;
-      mnh[p].push_back((uint32_t)v);
+    std::vector<SelectAttr> kept;
+    for (const auto& e : ent) kept.push_back(attrs[p][e.second]);
+    pref[p] = classRanks(kept);
+    for (size_t i = 0; i < ent.size(); ++i) {
+      ann[p].push_back(ent[i].first);
+      mnh[p].push_back(clampedMinNexthop(kept[i]));
     }
   }
+}
+
+// the dense class rank of each entry among the given ones: (pathPreference,
+// sourcePreference) descending, distance ascending
+// (selectRoutes(SHORTEST_DISTANCE), LsdbUtil.cpp:841-883)
+std::vector<uint32_t> LinkState::classRanks(const std::vector<SelectAttr>& attrs) {
+  using Cls = std::array<int64_t, 3>;
+  auto cls = [](const SelectAttr& a) { return Cls{a.pathPreference, a.sourcePreference, a.distance}; };
+  auto better = [](const Cls& a, const Cls& b) {
+    if (a[0] != b[0]) return a[0] > b[0];
+    if (a[1] != b[1]) return a[1] > b[1];
+    return a[2] < b[2];
+  };
+  std::vector<Cls> classes;
+  for (const auto& a : attrs) classes.push_back(cls(a));
+  std::sort(classes.begin(), classes.end(), better);
+  classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+  std::vector<uint32_t> out;
+  for (const auto& a : attrs)
+    out.push_back((uint32_t)(std::lower_bound(classes.begin(), classes.end(), cls(a), better) -
+                             classes.begin()));
+  return out;
+}
+
+uint32_t LinkState::clampedMinNexthop(const SelectAttr& a) {
+  return a.minNexthop ? (uint32_t)std::clamp<int64_t>(*a.minNexthop, 0, 0xFFFFFFFFll) : 0u;
+}
+
+// ---------------------------------------------------------------- select across areas
+LinkState::AreasResult LinkState::allAreasSelect(const std::vector<LinkState*>& given,
+                                                 const std::vector<std::vector<AreaEntry>>& prefixes,
+                                                 bool useLinkMetric) {
+  if (given.empty() || given.size() > 32)
+    throw std::invalid_argument("allAreasSelect: 1 .. 32 areas");
+  // the areas by name
+  AreasResult out;
+  out.order.resize(given.size());
+  for (size_t i = 0; i < given.size(); ++i) {
+    if (!given[i]) throw std::invalid_argument("allAreasSelect: null area");
+    out.order[i] = (uint32_t)i;
+  }
+  std::sort(out.order.begin(), out.order.end(),
+            [&](uint32_t a, uint32_t b) { return given[a]->area_ < given[b]->area_; });
+  std::vector<LinkState*> ar;
+  for (uint32_t i : out.order) ar.push_back(given[i]);
+  const size_t A = ar.size(), P = prefixes.size();
+  for (size_t a = 1; a < A; ++a)
+    if (ar[a]->area_ == ar[a - 1]->area_)
+      throw std::invalid_argument("allAreasSelect: area " + ar[a]->area_ + " given twice");
+  // the name union and each area's global ids
+  for (LinkState* ls : ar) {
+    ls->snapshot();
+    out.names.insert(out.names.end(), ls->csr_->names.begin(), ls->csr_->names.end());
+  }
+  std::sort(out.names.begin(), out.names.end());
+  out.names.erase(std::unique(out.names.begin(), out.names.end()), out.names.end());
+  const size_t G = out.names.size();
+  std::vector<std::vector<uint32_t>> gid(A);
+  for (size_t a = 0; a < A; ++a)
+    for (const auto& nm : ar[a]->csr_->names)
+      gid[a].push_back((uint32_t)(std::lower_bound(out.names.begin(), out.names.end(), nm) -
+                                  out.names.begin()));
+  // the table: an entry of an unknown area throws (the reference reads
+  // areaLinkStates.at(area)); a node unknown to its area is dropped with its
+  // attributes, of a (node, area) given twice the first counts; ascending in
+  // (node, area); class ranks and clamped thresholds over the kept entries
+  struct Ent {
+    uint32_t node, area, loc;
+    size_t at;
+  };
+  std::vector<uint32_t> off(P + 1, 0), tnode, tarea, tloc, tpref, tmnh;
+  for (size_t p = 0; p < P; ++p) {
+    std::vector<Ent> ent;
+    for (size_t i = 0; i < prefixes[p].size(); ++i) {
+      const AreaEntry& e = prefixes[p][i];
+      size_t a = 0;
+      while (a < A && ar[a]->area_ != e.area) ++a;
+      if (a == A) throw std::invalid_argument("prefix entry of unknown area " + e.area);
+      const auto it = ar[a]->csr_->ids.find(e.node);
+      if (it == ar[a]->csr_->ids.end()) continue;
+      ent.push_back(Ent{gid[a][it->second], (uint32_t)a, it->second, i});
+    }
+    std::stable_sort(ent.begin(), ent.end(), [](const Ent& x, const Ent& y) {
+      return x.node != y.node ? x.node < y.node : x.area < y.area;
+    });
+    ent.erase(std::unique(ent.begin(), ent.end(),
+                          [](const Ent& x, const Ent& y) { return x.node == y.node && x.area == y.area; }),
+              ent.end());
+    std::vector<SelectAttr> kept;
+    for (const auto& e : ent) kept.push_back(prefixes[p][e.at].attr);
+    const std::vector<uint32_t> ranks = classRanks(kept);
+    for (size_t i = 0; i < ent.size(); ++i) {
+      tnode.push_back(ent[i].node);
+      tarea.push_back(ent[i].area);
+      tloc.push_back(ent[i].loc);
+      tpref.push_back(ranks[i]);
+      tmnh.push_back(clampedMinNexthop(kept[i]));
+    }
+    off[p + 1] = (uint32_t)tnode.size();
+  }
+  out.prefixes = (uint32_t)P;
+  out.words.resize(A);
+  out.nh.resize(A);
+  for (size_t a = 0; a < A; ++a) {
+    out.words[a] = ar[a]->selectWords();
+    out.nh[a].assign(ar[a]->csr_->names.size() * P * out.words[a], 0);
+  }
+  out.metric.assign(G * P, kInf);
+  out.best.assign(G * P, kInf);
+  for (auto* v : {&out.count, &out.links, &out.need, &out.areas}) v->assign(G * P, 0);
+  out.installed.assign(G * P, 0);
+  if (!G || !P) return out;
+  auto install = [&] {
+    for (size_t i = 0; i < G * P; ++i) out.installed[i] = out.links[i] > 0 && out.need[i] <= out.links[i];
+  };
+  // the device path: every area on the engine, on one device of its own
+  auto deviceOk = [&] {
+    for (LinkState* ls : ar)
+      if (ls->hostRun(useLinkMetric) || ls->devices_.size() > 1 || ls->device_ != ar[0]->device_)
+        return false;
+    return true;
+  };
+  if (deviceOk()) {
+    // re-sweep the areas whose version moved (a device error there degrades
+    // that area: the host path below then answers)
+    for (LinkState* ls : ar) ls->prefetchAllSources(useLinkMetric);
+  }
+  if (deviceOk()) {
+    bool swept = true;
+    for (LinkState* ls : ar) swept = swept && ls->sweep_ && ls->sweepHas(useLinkMetric);
+    if (swept) {
+      std::vector<ospf_sweep*> sw;
+      std::vector<const uint32_t*> gp;
+      std::vector<uint32_t*> nhp;
+      for (size_t a = 0; a < A; ++a) {
+        sw.push_back(ar[a]->sweep_);
+        gp.push_back(gid[a].data());
+        nhp.push_back(out.nh[a].data());
+      }
+      const ospf_areas_table t{(uint32_t)A,     sw.data(),    gp.data(),    (uint32_t)G,
+                               (uint32_t)P,     off.data(),   tnode.data(), tarea.data(),
+                               tpref.data(),    tmnh.data()};
+      const ospf_areas_pout o{out.metric.data(), out.count.data(), out.links.data(),
+                              out.need.data(),   out.best.data(),  out.areas.data(),
+                              nhp.data(),        out.words.data()};
+      const int rc = ospf_areas_select_policy(&t, &o);
+      if (rc == OSPF_OK) {
+        out.onDevice = true;
+        install();
+        return out;
+      }
+      const EngineError err(rc, ospf_sweep_last_error(sw[0]));
+      // a device error (or the device out of memory) sends every area to its
+      // host path, as an error inside one LinkState's own call does: they
+      // share the device. All of them or none: an area that may not degrade
+      // makes the call throw with no area touched. Any other code (a contract
+      // or LDS-size refusal) is no fault of the device: this call alone is
+      // answered on the host.
+      if (rc == OSPF_E_DEVICE || rc == OSPF_E_NOMEM) {
+        for (LinkState* ls : ar)
+          if (!ls->degradeOnError_ || !ls->engineOpened_) throw err;
+        for (LinkState* ls : ar) ls->onEngineError(err);
+      }
+    }
+  }
+  // the host path: the same steps over every area's getSpfResult
+  std::vector<uint32_t> minw;
+  for (uint32_t g = 0; g < G; ++g) {
+    const std::string& me = out.names[g];
+    struct Mine {
+      const SpfResult* res = nullptr;
+      uint32_t la = kInf;
+      std::vector<uint32_t> nbrs, c;
+    };
+    std::vector<Mine> mine(A);
+    for (size_t a = 0; a < A; ++a) {
+      LinkState& ls = *ar[a];
+      const auto it = ls.csr_->ids.find(me);
+      if (it == ls.csr_->ids.end()) continue;
+      Mine& m = mine[a];
+      m.la = it->second;
+      m.res = &ls.getSpfResult(me, useLinkMetric);
+      const Csr& cs = *ls.csr_;
+      const uint32_t r = m.la;
+      m.nbrs = ls.nbrsOf(r);
+      // the links r - k getNextHopsThrift emits: up, at the smallest metric r
+      // advertises towards k (every up link under hop count)
+      minw.assign(m.nbrs.size(), kInf);
+      m.c.assign(m.nbrs.size(), 0);
+      auto slot = [&](uint32_t id) {
+        return (uint32_t)(std::lower_bound(m.nbrs.begin(), m.nbrs.end(), id) - m.nbrs.begin());
+      };
+      for (int pass = 0; pass < 2; ++pass)
+        for (uint32_t e = cs.rowPtr[r]; e < cs.rowPtr[r + 1]; ++e) {
+          if (cs.col[e] == r || !cs.edgeUp[e]) continue;
+          const uint32_t k = slot(cs.col[e]);
+          if (!pass) minw[k] = std::min(minw[k], cs.metric[e]);
+          else if (!useLinkMetric || cs.metric[e] == minw[k]) ++m.c[k];
+        }
+    }
+    for (size_t p = 0; p < P; ++p) {
+      const uint32_t lo = off[p], hi = off[p + 1];
+      auto nameOf = [&](uint32_t k) -> const std::string& { return out.names[tnode[k]]; };
+      // 1. reached in the entry's own area; 2. the best class
+      std::vector<uint32_t> R, S, Sf;
+      uint32_t top = kInf;
+      for (uint32_t k = lo; k < hi; ++k) {
+        const Mine& m = mine[tarea[k]];
+        if (!m.res || !m.res->count(nameOf(k))) continue;
+        R.push_back(k);
+        top = std::min(top, tpref[k]);
+      }
+      if (R.empty()) continue;
+      for (uint32_t k : R)
+        if (tpref[k] == top) S.push_back(k);
+      // 3. the drain filter, by the entry's own area
+      for (uint32_t k : S)
+        if (!ar[tarea[k]]->csr_->noTransit[tloc[k]]) Sf.push_back(k);
+      if (Sf.empty()) Sf = S;
+      // 4. / 5. per area of g with an entry of its own: the nodes of all of Sf
+      const size_t cell = (size_t)g * P + p;
+      Metric shortest = std::numeric_limits<Metric>::max();
+      std::vector<std::pair<size_t, std::vector<const std::string*>>> won;
+      for (size_t a = 0; a < A; ++a) {
+        const Mine& m = mine[a];
+        if (!m.res) continue;
+        bool own = false;
+        for (uint32_t k : Sf) own = own || tarea[k] == a;
+        if (!own) continue;
+        Metric ma = std::numeric_limits<Metric>::max();
+        std::vector<const std::string*> L;
+        uint32_t prev = kInf;
+        for (uint32_t k : Sf) {
+          if (tnode[k] == prev) continue;  // each node once
+          prev = tnode[k];
+          const auto it = m.res->find(nameOf(k));
+          if (it == m.res->end()) continue;
+          const Metric d = it->second.metric();
+          if (d < ma) {
+            ma = d;
+            L.clear();
+          }
+          if (d == ma) L.push_back(&nameOf(k));
+        }
+        if (L.empty() || ma > shortest) continue;
+        if (ma < shortest) {
+          shortest = ma;
+          won.clear();
+        }
+        won.emplace_back(a, std::move(L));
+      }
+      // 6. outputs
+      for (const auto& [a, L] : won) {
+        const Mine& m = mine[a];
+        const uint32_t W = out.words[a];
+        uint32_t* words = out.nh[a].data() + ((size_t)m.la * P + p) * W;
+        for (const std::string* d : L)
+          for (const auto& nhName : m.res->at(*d).nextHops()) {
+            const uint32_t id = ar[a]->csr_->ids.at(nhName);
+            const uint32_t k = (uint32_t)(std::lower_bound(m.nbrs.begin(), m.nbrs.end(), id) - m.nbrs.begin());
+            if (k < m.nbrs.size() && m.nbrs[k] == id && k / 32 < W) words[k / 32] |= 1u << (k % 32);
+          }
+        for (uint32_t k = 0; k < m.nbrs.size() && k / 32 < W; ++k)
+          if (words[k / 32] >> (k % 32) & 1u) out.links[cell] += m.c[k];
+        out.count[cell] += (uint32_t)L.size();
+        out.areas[cell] |= 1u << a;
+      }
+      out.metric[cell] = (uint32_t)shortest;
+      for (uint32_t k : Sf) out.need[cell] = std::max(out.need[cell], tmnh[k]);
+      out.best[cell] = S.front() - lo;
+      for (uint32_t k : S)
+        if (tnode[k] == g) {
+          out.best[cell] = k - lo;
+          break;
+        }
+    }
+  }
+  install();
+  return out;
 }
 
 LinkState::PolicyResult LinkState::allSourcesSelect(

@@ -571,7 +571,7 @@ class LinkState {
   // first occurrence counts; unknown names are dropped with their attributes.
   // On the host path the same rule runs over getSpfResult of every node.
   // Not covered: SR_MPLS per-destination next hops, KSP2 / per-area distance
-  // selection, BGP metric vectors, several areas.
+  // selection, BGP metric vectors. Several areas: allAreasSelect.
   struct SelectAttr {
     int64_t pathPreference = 0, sourcePreference = 0, distance = 0;
     std::optional<int64_t> minNexthop;
@@ -587,6 +587,47 @@ class LinkState {
                                 bool useLinkMetric = true, uint32_t nhWords = 0);
   // next-hop words of the widest node of the snapshot
   uint32_t selectWords();
+  // The same selection across several areas, one LinkState each
+  // (createRouteForPrefix is multi-area at its core, SpfSolver.cpp:229-244,
+  // :365-443; SpfSolver::prefixRoute restates it per node), for every node of
+  // the union of the areas and every prefix: ospf_areas_select_policy over
+  // the areas' resident sweeps. The areas are ordered by area name (`order`:
+  // position -> index into the given list), the union of their node names by
+  // name bytes (`names`: the global ids). Entries name (node, area); an
+  // unknown area throws std::invalid_argument, a node unknown to its area is
+  // dropped with its attributes, of a (node, area) given twice the first
+  // counts. The class ranks are policyTable's, over the (node, area) entries
+  // of a prefix. An area whose version moved is swept again. metric / count /
+  // links / need / best / areas / installed are [G][prefixes] by global id
+  // (best: the entry's position among the kept entries of its prefix in
+  // (node, area) order; areas: the mask of the winning areas by name rank),
+  // nh[a] is [V_a][prefixes][words[a]] by area a's node id. When an area is in
+  // host mode, multi-device, on another device or degraded, or when the
+  // engine call fails, the same steps run on the host over each area's
+  // getSpfResult. A device error or the device out of memory degrades every
+  // area (they share the device; all of them or, when one may not degrade,
+  // none and the error is thrown); any other engine refusal (contract, LDS
+  // size) sends only this call to the host.
+  // Not covered: a resident multi-area state and its delta, UCMP across
+  // areas, SR_MPLS per-destination next hops and KSP2, BGP metric vectors,
+  // several devices.
+  struct AreaEntry {
+    std::string node, area;
+    SelectAttr attr;
+  };
+  struct AreasResult {
+    std::vector<uint32_t> order;      // areas by name: index into the given list
+    std::vector<std::string> names;   // global id -> node name
+    uint32_t prefixes = 0;
+    std::vector<uint32_t> words;      // per area (name order)
+    std::vector<uint32_t> metric, count, links, need, best, areas;  // [G][prefixes]
+    std::vector<std::vector<uint32_t>> nh;                          // per area
+    std::vector<uint8_t> installed;                                 // [G][prefixes]
+    bool onDevice = false;
+  };
+  static AreasResult allAreasSelect(const std::vector<LinkState*>& areas,
+                                    const std::vector<std::vector<AreaEntry>>& prefixes,
+                                    bool useLinkMetric = true);
   // Only the selections a topology change altered: the counterpart of
   // DecisionRouteDb::calculateUpdate (SpfSolver.cpp:24-59) for
   // allSourcesSelect's route DB. trackSelect binds the LinkState to one
@@ -918,6 +959,10 @@ class LinkState {
                    const std::vector<std::vector<SelectAttr>>& attrs, const char* who,
                    std::vector<std::vector<uint32_t>>& ann, std::vector<std::vector<uint32_t>>& pref,
                    std::vector<std::vector<uint32_t>>& mnh) const;
+  // the dense class rank of each attribute set among the given ones, and the
+  // clamped threshold (policyTable's, shared with allAreasSelect)
+  static std::vector<uint32_t> classRanks(const std::vector<SelectAttr>& attrs);
+  static uint32_t clampedMinNexthop(const SelectAttr& a);
   // ---- trackSelect ----
   bool tracking_ = false, trackMetric_ = true;
   bool trackPolicy_ = false;       // tracked with attributes: the policy selection

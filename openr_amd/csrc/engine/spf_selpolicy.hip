@@ -23,7 +23,8 @@
 //
 // Out of scope (include/openr_spf.h says so too): SR_MPLS per-destination
 // next hops, K_SHORTEST_DISTANCE_2 and PER_AREA_SHORTEST_DISTANCE, BGP metric
-// vectors, several areas. (A policy table in ospf_selstate_*: spf_seldelta_policy.hip.)
+// vectors. (Several areas: spf_selareas.hip. A policy table in ospf_selstate_*:
+// spf_seldelta_policy.hip.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

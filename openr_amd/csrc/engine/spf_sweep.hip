@@ -315,6 +315,15 @@ void release(ospf_sweep* s) {
   s->d_pol_tab = nullptr;
   s->d_pol_roots = nullptr;  // one of allocs
   s->pol_tab_words = 0;
+  if (s->areas_ev) {
+    hipEventSynchronize(s->areas_ev);
+    hipEventDestroy(s->areas_ev);
+  }
+  if (s->d_areas_blob) hipFree(s->d_areas_blob);
+  s->areas_ev = nullptr;
+  s->d_areas_blob = nullptr;
+  s->d_area_rows = nullptr;  // one of allocs
+  s->areas_blob_bytes = 0;
   for (hipStream_t st : s->streams) {
     if (!st) continue;
     if (s->c) {

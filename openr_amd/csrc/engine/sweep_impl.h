@@ -80,6 +80,15 @@ struct ospf_sweep {
   uint32_t* d_pol_tab = nullptr;
   size_t pol_tab_words = 0;
   hipEvent_t pol_ev = nullptr;
+  // ospf_areas_select_policy*: every node's rows as a device table BY NODE ID
+  // (uploaded on first use; the sweep owns every root), and -- on area 0's
+  // sweep -- the last call's device block (per-area pointers, global -> local
+  // ids, the table; grown on demand) with the event after the launch that
+  // reads it
+  ospf_int::SelRow* d_area_rows = nullptr;
+  void* d_areas_blob = nullptr;
+  size_t areas_blob_bytes = 0;
+  hipEvent_t areas_ev = nullptr;
 };
 
 namespace ospf_int {

@@ -73,6 +73,93 @@ def _policy_host_out(n: int, P: int, W: int, want: Sequence[str]):
     return o, arrs
 
 
+AREAS_OUTPUTS = ("metric", "count", "links", "need", "best", "areas", "nh")
+
+
+def areas_table(sweeps: Sequence["Sweep"], gids: Sequence[Sequence[int]], n_global: int,
+                offsets: Sequence[int], node: Sequence[int], area: Sequence[int],
+                pref: Optional[Sequence[int]], min_nexthop: Optional[Sequence[int]] = None):
+    """(ospf_areas_table, the arrays it points into): one sweep and one
+    node id -> global id list per area (area-name order) and the CSR table of
+    (global node, area) entries with a class rank and optionally a minNexthop
+    threshold each. A sweep given as None passes NULL; pref None passes NULL."""
+    A = len(sweeps)
+    hs = (C.c_void_p * max(1, A))(*[None if s is None else s._h for s in sweeps])
+    gs = [np.ascontiguousarray(g, np.uint32) for g in gids]
+    gp = (C.c_void_p * max(1, A))(*[g.ctypes.data if g.size else None for g in gs])
+    off = np.ascontiguousarray(offsets, np.uint32)
+    cols = [None if c is None else np.ascontiguousarray(c, np.uint32)
+            for c in (node, area, pref, min_nexthop)]
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    t = N.ospf_areas_table(A, C.cast(hs, C.c_void_p), C.cast(gp, C.c_void_p), int(n_global),
+                           max(0, int(off.size) - 1), off.ctypes.data if off.size else None,
+                           *[ptr(c) for c in cols])
+    return t, (hs, gs, gp, off, cols)
+
+
+def _areas_last_error(sweeps) -> str:
+    s = sweeps[0] if len(sweeps) else None
+    return "" if s is None else s._L.ospf_sweep_last_error(s._h).decode()
+
+
+def select_policy_areas(sweeps: Sequence["Sweep"], gids: Sequence[Sequence[int]], n_global: int,
+                        offsets: Sequence[int], node: Sequence[int], area: Sequence[int],
+                        pref: Optional[Sequence[int]],
+                        min_nexthop: Optional[Sequence[int]] = None,
+                        nh_words: Optional[Sequence[int]] = None,
+                        want: Sequence[str] = AREAS_OUTPUTS) -> Dict[str, object]:
+    """ospf_areas_select_policy: the reference's best-route selection across
+    several areas (one sweep per area, area-name order) for every node of the
+    union and every prefix -> {metric, count, links, need, best, areas [G, P]
+    u32 by global id, nh: a list of [V_a, P, W_a] u32 by each area's node id};
+    only the outputs named in `want` are computed. best is the entry's
+    position within its prefix."""
+    bad = set(want) - set(AREAS_OUTPUTS)
+    if bad:
+        raise ValueError(f"unknown outputs {sorted(bad)}")
+    L = N.engine()
+    t, keep = areas_table(sweeps, gids, n_global, offsets, node, area, pref, min_nexthop)
+    G, P, A = int(n_global), int(t.n_prefixes), len(sweeps)
+    out: Dict[str, object] = {k: np.zeros((G, P), np.uint32) for k in want if k != "nh"}
+    W = np.ascontiguousarray(
+        nh_words if nh_words is not None else [max(1, s.max_nh_words) for s in sweeps], np.uint32)
+    nhp = None
+    if "nh" in want:
+        out["nh"] = [np.zeros((len(gids[a]), P, int(W[a])), np.uint32) for a in range(A)]
+        nhp = (C.c_void_p * max(1, A))(*[x.ctypes.data for x in out["nh"]])
+    o = N.ospf_areas_pout(*[out[k].ctypes.data if k in out else None for k in AREAS_OUTPUTS[:6]],
+                          C.cast(nhp, C.c_void_p) if nhp is not None else None, W.ctypes.data)
+    rc = L.ospf_areas_select_policy(C.byref(t), C.byref(o))
+    if rc != 0:
+        raise EngineError(rc, _areas_last_error(sweeps))
+    return out
+
+
+def select_policy_areas_dev(sweeps: Sequence["Sweep"], gids: Sequence[Sequence[int]],
+                            n_global: int, offsets: Sequence[int], node: Sequence[int],
+                            area: Sequence[int], pref: Optional[Sequence[int]],
+                            min_nexthop: Optional[Sequence[int]],
+                            nh_words: Optional[Sequence[int]], *, d_metric: int = 0,
+                            d_count: int = 0, d_links: int = 0, d_need: int = 0, d_best: int = 0,
+                            d_areas: int = 0, d_nh: Optional[Sequence[int]] = None,
+                            stream: int = 0) -> None:
+    """ospf_areas_select_policy_dev: the same into device memory (raw pointers;
+    0 = not wanted; d_nh one pointer per area), queued on `stream` after the
+    uploads."""
+    L = N.engine()
+    t, keep = areas_table(sweeps, gids, n_global, offsets, node, area, pref, min_nexthop)
+    A = len(sweeps)
+    W = None if nh_words is None else np.ascontiguousarray(nh_words, np.uint32)
+    nhp = None if d_nh is None else (C.c_void_p * max(1, A, len(d_nh)))(*[p or None for p in d_nh])
+    o = N.ospf_areas_pout(d_metric or None, d_count or None, d_links or None, d_need or None,
+                          d_best or None, d_areas or None,
+                          C.cast(nhp, C.c_void_p) if nhp is not None else None,
+                          W.ctypes.data if W is not None else None)
+    rc = L.ospf_areas_select_policy_dev(C.byref(t), C.byref(o), stream or None)
+    if rc != 0:
+        raise EngineError(rc, _areas_last_error(sweeps))
+
+
 # ospf_select_change / odl_select_change records
 CHANGE_DTYPE = np.dtype([("root", np.uint32), ("prefix", np.uint32), ("metric", np.uint32),
                          ("count", np.uint32)])

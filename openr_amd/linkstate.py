@@ -218,12 +218,74 @@ def route_dbs_multi(areas: Sequence["LinkState"], mes: Sequence[str], prefixes,
     return _parse_route_text(areas[0]._take(p), mes, with_area=True)
 
 
+def all_areas_select_policy(areas: Sequence["LinkState"], prefixes: Dict[str, Sequence[tuple]],
+                            use_link_metric: bool = True) -> dict:
+    """The reference's route selection across several areas, one LinkState
+    each, for every node of the union of the areas and every prefix
+    (odl_areas_select_policy; createRouteForPrefix, SpfSolver.cpp:197-458),
+    selected on the device from the areas' all-sources sweeps, or by the same
+    steps on the host when an area is in host mode or degraded. prefixes:
+    {prefix: [(node name, area name, path_pref, source_pref, distance,
+    min_nexthop_or_None), ...]}. Returns a dict: names (global id -> node name,
+    the union by name bytes), area_names (the areas by name: bit i of `areas`
+    and nh[i] belong to area_names[i]), metric / count / links / need / best /
+    areas [G, P] u32 by global id (best: the entry's position among the kept
+    entries of its prefix in (node, area) order), nh a list of [V_a, P, W_a]
+    u32 by that area's node id, installed [G, P] bool, on_device."""
+    L = N.decision()
+    A = len(areas)
+    hs = (C.c_void_p * max(1, A))(*[a._h for a in areas])
+    unset = -(1 << 63)
+    lines, attrs = [], []
+    for ents in prefixes.values():
+        f = []
+        for nm, ar, pp, sp, dist, mn in ents:
+            for x in (nm, ar):
+                if not x or "\n" in x or "\t" in x:
+                    raise ValueError("names must be non-empty, without tabs and newlines")
+            f += [nm, ar]
+            attrs.append((int(pp), int(sp), int(dist), unset if mn is None else int(mn)))
+        lines.append("\t".join(f))
+    at = np.ascontiguousarray(attrs, np.int64).reshape(-1, 4)
+    args = (hs, A, "\n".join(lines).encode(), len(lines), at.ctypes.data if at.size else None,
+            at.shape[0], int(use_link_metric))
+    G = C.c_uint32(0)
+    order = np.zeros(max(1, A), np.uint32)
+    words = np.zeros(max(1, A), np.uint32)
+    if L.odl_areas_select_policy(*args, C.byref(G), order.ctypes.data, words.ctypes.data,
+                                 *([None] * 10)) != 0:
+        raise LinkStateError(areas[0]._err())
+    P, g = len(lines), int(G.value)
+    out = {k: np.zeros((g, P), np.uint32)
+           for k in ("metric", "count", "links", "need", "best", "areas")}
+    by_name = [areas[int(i)] for i in order[:A]]
+    nh = [np.zeros((a.num_nodes(), P, int(w)), np.uint32) for a, w in zip(by_name, words)]
+    nhp = (C.c_void_p * max(1, A))(*[x.ctypes.data for x in nh])
+    inst = np.zeros((g, P), np.uint8)
+    names = C.c_void_p()
+    dev = C.c_int(0)
+    if L.odl_areas_select_policy(*args, C.byref(G), order.ctypes.data, words.ctypes.data,
+                                 C.byref(names), *[out[k].ctypes.data for k in
+                                                   ("metric", "count", "links", "need", "best",
+                                                    "areas")],
+                                 nhp, inst.ctypes.data, C.byref(dev)) != 0:
+        raise LinkStateError(areas[0]._err())
+    txt = areas[0]._take(names)
+    out["names"] = txt.split("\n")[:-1] if txt else []
+    out["area_names"] = [a.area for a in by_name]
+    out["nh"] = nh
+    out["installed"] = inst.astype(bool)
+    out["on_device"] = bool(dev.value)
+    return out
+
+
 class LinkState:
     """odl::LinkState over the MI355X SPF engine (device `device`)."""
 
     def __init__(self, area: str = "0", device: int = 0, stream: Optional[AdjDbStream] = None,
                  devices: Optional[Sequence[int]] = None):
         self._L = N.decision()
+        self.area = area
         h = C.c_void_p()
         if devices is not None and len(devices) > 1:
             devs = np.ascontiguousarray(devices, np.int32)

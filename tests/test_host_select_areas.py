@@ -1,0 +1,159 @@
+"""Route selection across several areas on the host path
+(linkstate.all_areas_select_policy with set_host_spf) and the expectation the
+GPU tests use (areas_ref.expect), both against the product's per-node route
+build: route_dbs_multi(best_route_selection=True), i.e. SpfSolver::prefixRoute
+over several areas (openr/decision/SpfSolver.cpp:197-458)."""
+import numpy as np
+import pytest
+
+import areas_ref as AR
+from graphs import metric_graph
+from openr_amd.adjdb import AdjDbStream
+from openr_amd.linkstate import (LinkState, all_areas_select_policy, root_neighbor_ids,
+                                 route_dbs_multi)
+from oracle import Oracle, parse_spf_text
+
+FF = 0xFFFFFFFF
+
+
+def host_area(name, links, overloaded=(), hop=False):
+    st = AdjDbStream.from_dbs(metric_graph(links, overloaded))
+    ls = LinkState(area=name)
+    ls.set_host_spf(True)
+    ls.apply(st)
+    names, csr = ls.node_names(), ls.csr()
+    orc = Oracle(st)
+    spf = {r: parse_spf_text(orc.spf_text(r, not hop)) for r in names}
+    return dict(name=name, ls=ls, names=names, csr=csr, spf=spf)
+
+
+def addr(p):
+    return f"::ffff:10.{p // 250}.{p % 250 + 1}.1/128"
+
+
+def product_tables(areas, table):
+    """the table as route_dbs_multi and all_areas_select_policy take it: class
+    rank r as path preference 1000 - r (the higher wins), threshold 0 as unset"""
+    gnames, _ = AR.union(areas)
+    routes, policy = {}, {}
+    for p, ents in enumerate(table):
+        routes[addr(p)] = [(gnames[n], "ip", "ecmp", 0, None, areas[a]["name"], mn or None,
+                            (1000 - r, 0, 0)) for n, a, r, mn in ents]
+        policy[addr(p)] = [(gnames[n], areas[a]["name"], 1000 - r, 0, 0, mn or None)
+                           for n, a, r, mn in ents]
+    return routes, policy
+
+
+def check_against_route_build(areas, table, exp):
+    """every non-announcing node's route of every prefix: igp cost, the
+    (neighbour, area) set decoded from nh, best, selected, and whether a route
+    exists against installed"""
+    gnames, gids = AR.union(areas)
+    routes, _ = product_tables(areas, table)
+    dbs = route_dbs_multi([a["ls"] for a in areas], gnames, routes, best_route_selection=True)
+    ids = [{n: i for i, n in enumerate(a["names"])} for a in areas]
+    checked = 0
+    for g, me in enumerate(gnames):
+        db = dbs[me]
+        for p, ents in enumerate(table):
+            if any(n == g for n, _, _, _ in ents):
+                continue
+            have = db is not None and addr(p) in db["routes"]
+            assert have == bool(exp["installed"][g, p]), (me, p)
+            if not have:
+                continue
+            assert db["routes"][addr(p)][0] == exp["metric"][g, p], (me, p)
+            hops = set()
+            for a, ar in enumerate(areas):
+                if me not in ids[a]:
+                    continue
+                la = ids[a][me]
+                nb = root_neighbor_ids(ar["csr"], la)
+                w = exp["nh"][a][la, p]
+                hops |= {(ar["names"][int(nb[k])], ar["name"]) for k in range(nb.size)
+                         if int(w[k // 32]) >> (k % 32) & 1}
+            got = {(x[1], x[6]) for x in db[("U", addr(p))]}
+            assert got == hops, (me, p)
+            assert len(db[("U", addr(p))]) == exp["links"][g, p], (me, p)
+            best, sel = db["best"][addr(p)]
+            e = ents[int(exp["best"][g, p])]
+            assert best == (gnames[e[0]], areas[e[1]]["name"]), (me, p)
+            want = {(gnames[ents[i][0]], areas[ents[i][1]]["name"]) for i in exp["selected"][g, p]}
+            assert set(sel) == want, (me, p)
+            checked += 1
+    assert checked
+
+
+def check_host_call(areas, table, exp, hop=False):
+    _, policy = product_tables(areas, table)
+    got = all_areas_select_policy([a["ls"] for a in areas], policy, use_link_metric=not hop)
+    assert got["names"] == AR.union(areas)[0] and not got["on_device"]
+    assert got["area_names"] == [a["name"] for a in areas]
+    # best counts positions among the kept entries: the tables here keep every entry
+    AR.assert_equal(got, exp)
+    assert np.array_equal(got["installed"], exp["installed"])
+
+
+def words_of(areas):
+    return [max(1, (max(len(root_neighbor_ids(a["csr"], r)) for r in range(len(a["names"]))) + 31)
+                // 32) for a in areas]
+
+
+def four_nodes(b_metric=10):
+    """MultiAreaBestPathCalculation's graphs: area "A" is 1 - 2 - 4, area "B"
+    1 - 3 - 4"""
+    return [host_area("A", [("1", "2", 10, 10), ("2", "4", 10, 10)]),
+            host_area("B", [("1", "3", b_metric, b_metric), ("3", "4", b_metric, b_metric)])]
+
+
+A_, B_ = 0, 1
+
+
+def test_four_node_entry_sets():
+    n1, n2, n3, n4 = range(4)
+    areas = four_nodes()
+    t = [[(n1, A_, 0, 0)], [(n2, A_, 0, 0)], [(n3, B_, 0, 0)], [(n4, B_, 0, 0)]]
+    exp, _ = AR.expect(areas, t, (1, 1))
+    assert exp["metric"].tolist() == [[0, 10, 10, 20], [10, 0, FF, FF], [FF, FF, 0, 10],
+                                      [20, 10, 10, 0]]
+    check_against_route_build(areas, t, exp)
+    check_host_call(areas, t, exp)
+    # "1" also originates ADDR[1] into B: node 4 uses both areas at metric 20
+    t[0] = [(n1, A_, 0, 0), (n1, B_, 0, 0)]
+    exp, facts = AR.expect(areas, t, (1, 1))
+    assert exp["metric"][n4, 0] == 20 and exp["areas"][n4, 0] == 3 and facts["tie"] > 0
+    check_against_route_build(areas, t, exp)
+    check_host_call(areas, t, exp)
+    # the shorter area: "4" announces in both areas, B wins with 6 against 20
+    areas = four_nodes(3)
+    t = [[(n4, A_, 0, 0), (n4, B_, 0, 0)]]
+    exp, facts = AR.expect(areas, t, (1, 1))
+    assert exp["metric"][n1, 0] == 6 and exp["areas"][n1, 0] == 2 and facts["shorter_area"] > 0
+    check_against_route_build(areas, t, exp)
+    check_host_call(areas, t, exp)
+
+
+@pytest.mark.parametrize("unit,sizes,nb,seed", [(True, (30, 34), 4, 23), (False, (30, 34), 3, 20),
+                                                (False, (24, 26, 22), 4, 24)])
+def test_random_areas(unit, sizes, nb, seed):
+    areas = [host_area(f"a{i}", links, over)
+             for i, (links, over) in enumerate(AR.random_area_links(seed, sizes, nb, unit,
+                                                                    p=0.15))]
+    table = AR.random_entries(areas, np.random.default_rng(8), sizes=(0, 1, 2, 3, 5, 9, 20),
+                              singles=24)
+    exp, facts = AR.expect(areas, table, words_of(areas))
+    for k in ("tie", "shorter_area", "cross_area", "skipped_area", "single_area_root", "filtered",
+              "need_from_loser", "withheld", "best_outside"):
+        assert facts[k] > 0, (k, facts)
+    check_against_route_build(areas, table, exp)
+    check_host_call(areas, table, exp)
+
+
+def test_unknown_area_and_unknown_node():
+    areas = four_nodes()
+    ls = [a["ls"] for a in areas]
+    with pytest.raises(Exception, match="unknown area"):
+        all_areas_select_policy(ls, {addr(0): [("1", "C", 0, 0, 0, None)]})
+    # a node unknown to its area is dropped with its attributes
+    got = all_areas_select_policy(ls, {addr(0): [("3", "A", 9, 0, 0, 5), ("2", "A", 0, 0, 0, None)]})
+    assert got["metric"][:, 0].tolist() == [10, 0, FF, 10] and not got["need"].any()

@@ -2223,13 +2223,14 @@ LinkState::UcmpAll LinkState::allSourcesUcmp(UcmpAlgo algo,
     UcmpAll out;
     out.prefixes = (uint32_t)P;
     ucmpDev_ = ucmpHostOk_ = false;
-    if (trackDev_ && !hostRun(trackMetric_) && devices_.size() == 1) {
-      std::vector<int64_t> flat;
-      for (const auto& l : w) flat.insert(flat.end(), l.begin(), l.end());
-      // S per (node, distinct neighbour): the node's link weights over the
-      // tight links (up, at the smallest metric towards the neighbour; every
-      // up link under hop count), slots in nbrsOf order, node after node
-      std::vector<int64_t> S;
+    // S per (node, distinct neighbour): the node's link weights over the
+    // tight links (up, at the smallest metric towards the neighbour; every
+    // up link under hop count), slots in nbrsOf order, node after node.
+    // False when a link weight is negative or a slot's sum leaves i63: the
+    // engine takes sums in [0, 2^63 - 1] only, so that call is the host
+    // loop's, as with a metric outside the engine contract.
+    std::vector<int64_t> S;
+    const auto linkSums = [&] {
       for (uint32_t u = 0; u < V; ++u) {
         uint32_t e = csr_->rowPtr[u];
         const uint32_t hi = csr_->rowPtr[u + 1];
@@ -2245,11 +2246,17 @@ LinkState::UcmpAll LinkState::allSourcesUcmp(UcmpAlgo algo,
               best = m;
               sum = 0;
             }
-            sum += csr_->links.at(csr_->linkId[e])->weightFrom(csr_->names[u]);
+            const int64_t lw = csr_->links.at(csr_->linkId[e])->weightFrom(csr_->names[u]);
+            if (lw < 0 || __builtin_add_overflow(sum, lw, &sum)) return false;
           }
           if (k != u) S.push_back(sum);
         }
       }
+      return true;
+    };
+    if (trackDev_ && !hostRun(trackMetric_) && devices_.size() == 1 && linkSums()) {
+      std::vector<int64_t> flat;
+      for (const auto& l : w) flat.insert(flat.end(), l.begin(), l.end());
       const auto t0 = std::chrono::steady_clock::now();
       const int rc = ospf_selstate_ucmp(selstate_, (uint32_t)algo, flat.data(), S.data(),
                                         (uint32_t)S.size(), &out.rounds);

@@ -54,8 +54,12 @@ class Consts:
         for u in range(V):
             nb = R.root_neighbor_ids(csr, u).tolist()
             lo, hi = int(csr["row_ptr"][u]), int(csr["row_ptr"][u + 1])
+            up = {}  # neighbour -> its up entries (one pass: a hub of 2,100 spokes)
+            for e in range(lo, hi):
+                if csr["edge_up"][e]:
+                    up.setdefault(int(csr["col"][e]), []).append(e)
             for k in nb:
-                es = [e for e in range(lo, hi) if int(csr["col"][e]) == k and csr["edge_up"][e]]
+                es = up.get(k, [])
                 if use_link_metric and es:
                     m = min(int(csr["metric"][e]) for e in es)
                     es = [e for e in es if int(csr["metric"][e]) == m]
@@ -65,10 +69,26 @@ class Consts:
             self.dn_off[u + 1] = len(dn)
         self.dn = np.array(dn, np.uint32)
         self.c = np.array(c, np.int64)
-        self.S = np.array(S, np.int64)
+        # a sum beyond i63 (link weights the engine does not take) stays a Python integer
+        self.S = np.array(S, np.int64 if max(S, default=0) <= I63 else object)
 
     def slots(self, u):
         return range(int(self.dn_off[u]), int(self.dn_off[u + 1]))
+
+    def slot(self, u, k):
+        """the slot of node u's distinct neighbour k"""
+        lo = int(self.dn_off[u])
+        return lo + self.dn[lo:int(self.dn_off[u + 1])].tolist().index(k)
+
+    def with_S(self, sums):
+        """a copy with S overridden: sums = {(node, neighbour): link weight sum}
+        (the 'adj' limits are reached through S, whatever the links carry)"""
+        import copy
+        out = copy.copy(self)
+        out.S = self.S.copy()
+        for (u, k), s in sums.items():
+            out.S[self.slot(u, k)] = s
+        return out
 
 
 def bits(words):

@@ -242,15 +242,54 @@ int odl_all_sources_select_policy(odl_ls* ls, const char* prefixes_nl, uint32_t 
  * entry's position among the kept entries of its prefix in (node, area)
  * order), installed [G][n_prefixes] bytes, nh[i] [V_i][n_prefixes]
  * [nh_words[i]] by that area's node id. *on_device: 1 when the device
- * answered. Errors (-1) are reported on areas[0]. Not covered: a resident
- * multi-area state and its delta, UCMP across areas, SR_MPLS per-destination
- * next hops and KSP2, BGP metric vectors, several devices. */
+ * answered. Errors (-1) are reported on areas[0]. The same selection kept
+ * resident and its delta: odl_areas_track below. Not covered: UCMP across
+ * areas, SR_MPLS per-destination next hops and KSP2, BGP metric vectors,
+ * several devices. */
 int odl_areas_select_policy(odl_ls* const* areas, uint32_t n_areas, const char* prefixes_nl,
                             uint32_t n_prefixes, const int64_t* attrs, uint32_t n_attrs,
                             int use_link_metric, uint32_t* n_global, uint32_t* order,
                             uint32_t* nh_words, char** names_nl, uint32_t* metric, uint32_t* count,
                             uint32_t* links, uint32_t* need, uint32_t* best, uint32_t* areas_mask,
                             uint32_t* const* nh, uint8_t* installed, int* on_device);
+/* odl_areas_select_policy's route DB kept resident, and only the cells an
+ * event in some area or a change of the entries' attributes altered
+ * (LinkState::AreasTracker over ospf_areastate_*; calculateUpdate across
+ * areas). The tracker is bound to the given areas, which must outlive it, and
+ * to one table (the lines and attributes of odl_areas_select_policy).
+ *   odl_areas_delta     sweeps again every area whose version moved and returns
+ *                       malloc'ed lists (odl_free_buf): 32-B records {root,
+ *                       prefix, metric, count, links, need, best, areas} with
+ *                       the NEW values by global id, nh [n_changes][sum of
+ *                       nh_words] (area i's words one after the other, areas in
+ *                       name order), the rebased global roots. nh_words
+ *                       [n_areas]. *full: the node-name set of an area changed;
+ *                       a new baseline was made and no lists are returned.
+ *                       *on_device: 0 when the host path answered (an area in
+ *                       host mode, multi-device or degraded, or an engine
+ *                       error: the previous result is first copied off the
+ *                       device, so the delta is still answered).
+ *   odl_areas_tracked   the committed cells of some global nodes, in `nodes`
+ *                       order: columns [n][prefixes], nh[i] [n][prefixes]
+ *                       [nh_words[i]], zero where area i does not hold the
+ *                       node. With every output but order / nh_words NULL it
+ *                       only reports those two (what sizes nh).
+ *   odl_areas_set_attrs new attributes for the same entries, four per entry in
+ *                       table order; applied by the next odl_areas_delta.
+ * Errors (-1) are reported on the first area given to odl_areas_track. */
+typedef struct odl_areas_tracker odl_areas_tracker;
+int odl_areas_track(odl_ls* const* areas, uint32_t n_areas, const char* prefixes_nl,
+                    uint32_t n_prefixes, const int64_t* attrs, uint32_t n_attrs,
+                    int use_link_metric, odl_areas_tracker** out);
+int odl_areas_untrack(odl_areas_tracker* t);
+int odl_areas_set_attrs(odl_areas_tracker* t, const int64_t* attrs, uint32_t n_attrs);
+int odl_areas_delta(odl_areas_tracker* t, uint32_t* n_changes, uint32_t* n_rebased,
+                    uint32_t* nh_words, int* full, int* on_device, void** changes, void** nh,
+                    void** rebased);
+int odl_areas_tracked(odl_areas_tracker* t, const char* nodes_nl, uint32_t n, uint32_t* order,
+                      uint32_t* nh_words, uint32_t* metric, uint32_t* count, uint32_t* links,
+                      uint32_t* need, uint32_t* best, uint32_t* areas_mask, uint32_t* const* nh,
+                      uint8_t* installed);
 /* Only the selections a topology change altered (LinkState::trackSelect /
  * selectDelta / selectTracked): DecisionRouteDb::calculateUpdate
  * (SpfSolver.cpp:24-59) for odl_all_sources_select's route DB.

@@ -782,9 +782,9 @@ int ospf_sweep_select_policy(ospf_sweep* sw, const ospf_select_ptable* table, ui
  * holds, an entry whose node is absent from its area, entries not strictly
  * ascending in (node, area), area >= n_areas, pref >= 2^31 or NULL with
  * entries, an nh_words[a] too small. n_prefixes == 0: OSPF_OK, nothing written.
- * Not covered: a resident multi-area state and its delta, UCMP across areas,
- * SR_MPLS per-destination next hops and KSP2, BGP metric vectors, ospf_msweep
- * and several devices. */
+ * The same selection kept resident and its delta: ospf_areastate_* below.
+ * Not covered: UCMP across areas, SR_MPLS per-destination next hops and KSP2,
+ * BGP metric vectors, ospf_msweep and several devices. */
 typedef struct ospf_areas_table { /* host memory */
   uint32_t n_areas;               /* 1 .. 32 */
   ospf_sweep* const* sweeps;      /* [n_areas] */
@@ -979,6 +979,79 @@ int ospf_selstate_update_policy(ospf_selstate* st, ospf_sweep* sw, uint32_t nh_w
 int ospf_selstate_copy_policy(ospf_selstate* st, const uint32_t* roots, uint32_t n,
                               uint32_t nh_words, const ospf_select_pout* out);
 int ospf_selstate_set_policy(ospf_selstate* st, const uint32_t* pref, const uint32_t* min_nexthop);
+/* ospf_areas_select_policy's selection kept resident, and only the cells a
+ * re-sweep of some areas (or a change of the entries' attributes) changed:
+ * calculateUpdate for the multi-area route DB. An ospf_areastate holds one
+ * ospf_areas_table, copied at create (n_areas, n_global, every gid[a], offsets
+ * / node / area / pref / min_nexthop; the table's contract and errors as
+ * above), and is bound to the contexts behind table->sweeps[a], which are read
+ * at create for their context and node count V_a only (a sweep lives for one
+ * graph version, the state does not). Per global root g it keeps, by global
+ * id, SoA, no padding and twice (double-buffered): metric [P], count [P],
+ * links [P], need [P], best [P], areas [P], then for every area a that holds
+ * g nh_a [P][W_a(g)] in the root's own width in that area -- two buffers of
+ * the sum over g of P * (6 + the sum over g's areas of W_a(g)) * 4 bytes --
+ * and every area's distinct-neighbour lists for the rebase test. The calls are
+ * ospf_selstate_update_policy's restated over areas:
+ *   prime       stores the sweeps' selection as the baseline; reports nothing.
+ *   update      computes the sweeps' selection into the shadow buffer (its own
+ *               offsets: a W_a(g) may have changed), compares it on the device
+ *               and returns the cells that changed, then commits by swapping.
+ *               A cell is exactly what ospf_areas_select_policy defines; it
+ *               changed when any of its six header words or any next-hop word
+ *               of any area of the root differs. A record carries the NEW
+ *               values; installed = links > 0 && need <= links is the
+ *               caller's to derive. nh[i] is record i's areas one after the
+ *               other: area a's words start at word sum of nh_words[b], b < a,
+ *               zero-padded to nh_words[a] (>= that sweep's max_nh_words), and
+ *               zero for an area that did not win or does not hold the root.
+ *               A cell whose R became empty comes back as metric =
+ *               OSPF_DIST_INF, count = links = areas = 0, best = 0xFFFFFFFF.
+ *               The order of the records is unspecified. A global root whose
+ *               distinct-neighbour list differs in any one of its areas
+ *               between the stored version and the sweeps' graphs is rebased:
+ *               reported once in rebased_roots (global ids), its cells written
+ *               and not compared; the caller reads them with copy.
+ *   copy        the committed cells of `roots` (global ids) in `roots` order:
+ *               the six columns [n][P], nh[a] [n][P][nh_words[a]] (zero for an
+ *               area that does not hold the root); any output may be NULL.
+ *   set_policy  replaces pref / min_nexthop (the same checks; min_nexthop
+ *               NULL: all unset). Nothing committed changes: the next update,
+ *               even with the same sweeps, reports what the attributes changed.
+ * sweeps[a] must satisfy ospf_areas_select_policy's rules (has run, current
+ * against its context, owns every root, one device, one metric mode) and
+ * belong to the state's context a with the V_a the state was created with:
+ * anything else is OSPF_E_INVAL with the state untouched (a node added to or
+ * removed from an area is the caller's cue to create a new state). update /
+ * copy before prime: OSPF_E_INVAL. n_prefixes == 0: OSPF_OK with zero counts.
+ * n_changes > cap or n_rebased > cap_rebased: OSPF_E_RANGE with both counts
+ * complete; the state is UNCHANGED and the lists are to be ignored -- a retry
+ * with larger capacities returns the whole set. A root whose link counts do
+ * not fit the LDS: OSPF_E_RANGE, as from the select call. Any failure (an
+ * injected one on any area's context included) leaves the state as it was.
+ * When one of its contexts is closed the state releases its device memory and
+ * every later call on it but destroy is OSPF_E_INVAL. Errors through
+ * ospf_areastate_last_error. */
+typedef struct ospf_areastate ospf_areastate;
+typedef struct ospf_areas_change {
+  uint32_t root, prefix, metric, count, links, need, best, areas;
+} ospf_areas_change;
+int ospf_areastate_create(const ospf_areas_table* table, ospf_areastate** out);
+int ospf_areastate_destroy(ospf_areastate* st);
+const char* ospf_areastate_last_error(const ospf_areastate* st);
+/* device memory the state holds now (both buffers, lists, the table) */
+uint64_t ospf_areastate_device_bytes(const ospf_areastate* st);
+int ospf_areastate_prime(ospf_areastate* st, ospf_sweep* const* sweeps /*[n_areas]*/);
+int ospf_areastate_update(ospf_areastate* st, ospf_sweep* const* sweeps,
+                          const uint32_t* nh_words /*[n_areas]*/, ospf_areas_change* changes,
+                          uint32_t* nh /*[cap][sum of nh_words]*/, uint32_t cap,
+                          uint32_t* n_changes, uint32_t* rebased_roots, uint32_t cap_rebased,
+                          uint32_t* n_rebased);
+/* out->nh_words is read when out->nh is given */
+int ospf_areastate_copy(ospf_areastate* st, const uint32_t* roots, uint32_t n,
+                        const ospf_areas_pout* out);
+int ospf_areastate_set_policy(ospf_areastate* st, const uint32_t* pref,
+                              const uint32_t* min_nexthop);
 /* Time every launch unit alone on its stream: reps (>= 1) timed launches
  * after one untimed one; fills min(cap, n_launches) records. The sweep must
  * have run once. */
@@ -1052,7 +1125,9 @@ uint64_t ospf_spf_runs(const ospf_ctx* ctx);
  * ospf_msweep_select_policy (per part) / ospf_selstate_prime /
  * ospf_selstate_update / ospf_selstate_copy / ospf_selstate_ucmp /
  * ospf_selstate_ucmp_copy / ospf_selstate_update_policy /
- * ospf_selstate_copy_policy / ospf_selstate_set_policy on this context fails with
+ * ospf_selstate_copy_policy / ospf_selstate_set_policy / ospf_areastate_prime /
+ * ospf_areastate_update / ospf_areastate_copy / ospf_areastate_set_policy (on
+ * any of the state's contexts) on this context fails with
  * OSPF_E_DEVICE and does nothing (0 = off). Lets the caller's handling of a
  * device error be tested without a faulting GPU. */
 int ospf_inject_error(ospf_ctx* ctx, uint32_t after_calls);

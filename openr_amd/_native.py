@@ -48,6 +48,9 @@ ENGINE_SYMBOLS = [
     "ospf_selstate_ucmp", "ospf_selstate_ucmp_copy", "ospf_selstate_ucmp_info",
     "ospf_selstate_create_policy", "ospf_selstate_update_policy", "ospf_selstate_copy_policy",
     "ospf_selstate_set_policy",
+    "ospf_areastate_create", "ospf_areastate_destroy", "ospf_areastate_last_error",
+    "ospf_areastate_device_bytes", "ospf_areastate_prime", "ospf_areastate_update",
+    "ospf_areastate_copy", "ospf_areastate_set_policy",
     "ospf_multi_open", "ospf_multi_close", "ospf_multi_last_error", "ospf_multi_size",
     "ospf_multi_ctx", "ospf_multi_load_graph", "ospf_msweep_create", "ospf_msweep_destroy",
     "ospf_msweep_run", "ospf_msweep_digests", "ospf_msweep_part", "ospf_msweep_owner",
@@ -63,6 +66,8 @@ DECISION_SYMBOLS = [
     "odl_last_decode_error", "odl_get_counters", "odl_last_engine_error", "odl_inject_engine_error",
     "odl_set_degrade", "odl_all_sources_select", "odl_all_sources_select_policy",
     "odl_areas_select_policy",
+    "odl_areas_track", "odl_areas_untrack", "odl_areas_set_attrs", "odl_areas_delta",
+    "odl_areas_tracked",
     "odl_track_select", "odl_select_delta", "odl_select_tracked",
     "odl_track_select_policy", "odl_policy_delta", "odl_policy_tracked", "odl_set_tracked_attrs",
     "odl_all_sources_ucmp", "odl_ucmp_tracked", "odl_ucmp_host_loop",
@@ -274,6 +279,17 @@ def engine() -> C.CDLL:
                                                   C.POINTER(u32)]
         L.ospf_selstate_copy_policy.argtypes = [vp, vp, u32, u32, C.POINTER(ospf_select_pout)]
         L.ospf_selstate_set_policy.argtypes = [vp, vp, vp]
+        L.ospf_areastate_create.argtypes = [C.POINTER(ospf_areas_table), C.POINTER(vp)]
+        L.ospf_areastate_destroy.argtypes = [vp]
+        L.ospf_areastate_last_error.argtypes = [vp]
+        L.ospf_areastate_last_error.restype = cp
+        L.ospf_areastate_device_bytes.argtypes = [vp]
+        L.ospf_areastate_device_bytes.restype = u64
+        L.ospf_areastate_prime.argtypes = [vp, vp]
+        L.ospf_areastate_update.argtypes = [vp, vp, vp, vp, vp, u32, C.POINTER(u32), vp, u32,
+                                            C.POINTER(u32)]
+        L.ospf_areastate_copy.argtypes = [vp, vp, u32, C.POINTER(ospf_areas_pout)]
+        L.ospf_areastate_set_policy.argtypes = [vp, vp, vp]
         L.ospf_sweep_profile.argtypes = [vp, u32, vp, u32]
         L.ospf_sweep_graph_memsets.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.ospf_multi_open.argtypes = [vp, u32, C.POINTER(vp)]
@@ -317,6 +333,12 @@ def decision() -> C.CDLL:
                                        C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.odl_select_tracked.argtypes = [vp, cp, u32, u32, vp, vp, vp]
         L.odl_areas_select_policy.argtypes = [vp, u32, cp, u32, vp, u32, i32] + [vp] * 13
+        L.odl_areas_track.argtypes = [vp, u32, cp, u32, vp, u32, i32, C.POINTER(vp)]
+        L.odl_areas_untrack.argtypes = [vp]
+        L.odl_areas_set_attrs.argtypes = [vp, vp, u32]
+        L.odl_areas_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), vp, C.POINTER(i32),
+                                      C.POINTER(i32)] + [C.POINTER(vp)] * 3
+        L.odl_areas_tracked.argtypes = [vp, cp, u32] + [vp] * 10
         L.odl_track_select_policy.argtypes = [vp, cp, u32, vp, u32, i32]
         L.odl_policy_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
                                        C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]

@@ -27,7 +27,7 @@ ENGINE_SRC = [os.path.join(PKG, "csrc", "engine", f)
                         "spf_sweep.hip", "sweep_units.hip", "sweep_plan_derive.hip",
                         "sweep_plan_weighted.hip", "spf_multi.hip", "spf_select.hip", "spf_seldelta.hip",
                         "spf_ucmp.hip", "spf_selpolicy.hip", "spf_seldelta_policy.hip",
-                        "spf_selareas.hip")]
+                        "spf_selareas.hip", "spf_seldelta_areas.hip")]
 DECISION_SRC = [os.path.join(PKG, "csrc", "decision", f)
                 for f in ("link_state.cpp", "spf_solver.cpp", "adjdb_thrift.cpp", "decision_capi.cpp")]
 ENGINE_SO = os.path.join(LIB, "libopenr_spf_hip.so")
@@ -36,7 +36,7 @@ HEADERS = [os.path.join(ROOT, "include", h)
            for h in ("openr_spf.h", "openr_decision.h", "openr_adjdb.h")] + \
     [os.path.join(PKG, "csrc", "engine", h) for h in ("spf_kernels.h", "spf_internal.h", "sweep_impl.h", "host_pool.h",
                                                         "spf_select_dev.h", "spf_selstate.h",
-                                                        "spf_selpolicy_dev.h")] + \
+                                                        "spf_selpolicy_dev.h", "spf_selareas_dev.h")] + \
     [os.path.join(PKG, "csrc", "common", "knobs.h")]
 DECISION_HEADERS = HEADERS + \
     [os.path.join(PKG, "csrc", "decision", h) for h in ("link_state.h", "spf_solver.h", "adjdb_thrift.h")]

@@ -572,6 +572,43 @@ int odl_all_sources_select_policy(odl_ls* h, const char* prefixes_nl, uint32_t n
   }, -1);
 }
 
+namespace {
+// lines of tab-separated (node, area) name pairs with four attributes per entry
+std::vector<std::vector<odl::LinkState::AreaEntry>> areaEntries(const char* prefixes_nl,
+                                                                uint32_t n_prefixes,
+                                                                const int64_t* attrs,
+                                                                uint32_t n_attrs) {
+  std::vector<std::vector<odl::LinkState::AreaEntry>> prefixes;
+  size_t used = 0;
+  for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
+    std::vector<std::string> f;
+    for (size_t b = 0; b <= ln.size();) {  // tab-separated pairs
+      size_t e = ln.find('\t', b);
+      if (e == std::string::npos) e = ln.size();
+      if (e > b || b < ln.size()) f.emplace_back(ln, b, e - b);
+      b = e + 1;
+    }
+    if (f.size() % 2) throw std::invalid_argument("prefix line: node and area names in pairs");
+    std::vector<odl::LinkState::AreaEntry> es;
+    for (size_t i = 0; i < f.size(); i += 2) {
+      if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than entries");
+      const int64_t* a = attrs + 4 * used++;
+      odl::LinkState::AreaEntry e;
+      e.node = f[i];
+      e.area = f[i + 1];
+      e.attr.pathPreference = a[0];
+      e.attr.sourcePreference = a[1];
+      e.attr.distance = a[2];
+      if (a[3] != std::numeric_limits<int64_t>::min()) e.attr.minNexthop = a[3];
+      es.push_back(std::move(e));
+    }
+    prefixes.push_back(std::move(es));
+  }
+  if (used != n_attrs) throw std::invalid_argument("more attribute sets than entries");
+  return prefixes;
+}
+}  // namespace
+
 int odl_areas_select_policy(odl_ls* const* areas, uint32_t n_areas, const char* prefixes_nl,
                             uint32_t n_prefixes, const int64_t* attrs, uint32_t n_attrs,
                             int use_link_metric, uint32_t* n_global, uint32_t* order,
@@ -589,34 +626,8 @@ int odl_areas_select_policy(odl_ls* const* areas, uint32_t n_areas, const char* 
     if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
     if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
     std::vector<std::vector<odl::LinkState::AreaEntry>> prefixes;
-    size_t used = 0;
     // the need query reads no table
-    if (names_nl)
-      for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
-        std::vector<std::string> f;
-        for (size_t b = 0; b <= ln.size();) {  // tab-separated pairs
-          size_t e = ln.find('\t', b);
-          if (e == std::string::npos) e = ln.size();
-          if (e > b || b < ln.size()) f.emplace_back(ln, b, e - b);
-          b = e + 1;
-        }
-        if (f.size() % 2) throw std::invalid_argument("prefix line: node and area names in pairs");
-        std::vector<odl::LinkState::AreaEntry> es;
-        for (size_t i = 0; i < f.size(); i += 2) {
-          if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than entries");
-          const int64_t* a = attrs + 4 * used++;
-          odl::LinkState::AreaEntry e;
-          e.node = f[i];
-          e.area = f[i + 1];
-          e.attr.pathPreference = a[0];
-          e.attr.sourcePreference = a[1];
-          e.attr.distance = a[2];
-          if (a[3] != std::numeric_limits<int64_t>::min()) e.attr.minNexthop = a[3];
-          es.push_back(std::move(e));
-        }
-        prefixes.push_back(std::move(es));
-      }
-    if (names_nl && used != n_attrs) throw std::invalid_argument("more attribute sets than entries");
+    if (names_nl) prefixes = areaEntries(prefixes_nl, n_prefixes, attrs, n_attrs);
     const auto r = odl::LinkState::allAreasSelect(ls, prefixes, use_link_metric != 0);
     if (n_global) *n_global = (uint32_t)r.names.size();
     if (order) std::copy(r.order.begin(), r.order.end(), order);
@@ -646,6 +657,121 @@ int odl_areas_select_policy(odl_ls* const* areas, uint32_t n_areas, const char* 
     return 0;
   }, -1);
 }
+
+// ---------------------------------------------------------------- the areas tracker
+struct odl_areas_tracker {
+  odl_ls* first;  // errors are reported on it
+  std::unique_ptr<odl::LinkState::AreasTracker> t;
+};
+
+int odl_areas_track(odl_ls* const* areas, uint32_t n_areas, const char* prefixes_nl,
+                    uint32_t n_prefixes, const int64_t* attrs, uint32_t n_attrs,
+                    int use_link_metric, odl_areas_tracker** out) {
+  if (!areas || n_areas == 0 || !areas[0] || !out) return -1;
+  *out = nullptr;
+  return guard(areas[0], [&]() -> int {
+    std::vector<odl::LinkState*> ls;
+    for (uint32_t i = 0; i < n_areas; ++i) {
+      if (!areas[i]) throw std::invalid_argument("null area handle");
+      ls.push_back(&areas[i]->ls);
+    }
+    if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
+    if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
+    auto t = odl::LinkState::trackAreasSelect(
+        ls, areaEntries(prefixes_nl, n_prefixes, attrs, n_attrs), use_link_metric != 0);
+    *out = new odl_areas_tracker{areas[0], std::move(t)};
+    return 0;
+  }, -1);
+}
+
+int odl_areas_untrack(odl_areas_tracker* t) {
+  if (!t) return -1;
+  delete t;
+  return 0;
+}
+
+int odl_areas_set_attrs(odl_areas_tracker* t, const int64_t* attrs, uint32_t n_attrs) {
+  if (!t) return -1;
+  return guard(t->first, [&]() -> int {
+    if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
+    auto p = t->t->prefixes();
+    size_t used = 0;
+    for (auto& es : p)
+      for (auto& e : es) {
+        if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than entries");
+        const int64_t* a = attrs + 4 * used++;
+        e.attr = odl::LinkState::SelectAttr{};
+        e.attr.pathPreference = a[0];
+        e.attr.sourcePreference = a[1];
+        e.attr.distance = a[2];
+        if (a[3] != std::numeric_limits<int64_t>::min()) e.attr.minNexthop = a[3];
+      }
+    if (used != n_attrs) throw std::invalid_argument("more attribute sets than entries");
+    t->t->setAttrs(p);
+    return 0;
+  }, -1);
+}
+
+int odl_areas_delta(odl_areas_tracker* t, uint32_t* n_changes, uint32_t* n_rebased,
+                    uint32_t* nh_words, int* full, int* on_device, void** changes, void** nh,
+                    void** rebased) {
+  if (!t) return -1;
+  return guard(t->first, [&]() -> int {
+    if (!n_changes || !n_rebased || !nh_words || !full || !on_device || !changes || !nh || !rebased)
+      throw std::invalid_argument("null output pointer");
+    *changes = *nh = *rebased = nullptr;
+    const auto d = t->t->delta();
+    static_assert(sizeof(odl::LinkState::AreasChange) == 32, "odl_areas_change layout");
+    void* a = dupVec(d.changes);
+    void* b = nullptr;
+    void* c = nullptr;
+    try {
+      b = dupVec(d.nh);
+      c = dupVec(d.rebased);
+    } catch (...) {
+      std::free(a);
+      std::free(b);
+      throw;
+    }
+    *changes = a;
+    *nh = b;
+    *rebased = c;
+    *n_changes = (uint32_t)d.changes.size();
+    *n_rebased = (uint32_t)d.rebased.size();
+    std::copy(d.words.begin(), d.words.end(), nh_words);
+    *full = d.full ? 1 : 0;
+    *on_device = d.onDevice ? 1 : 0;
+    return 0;
+  }, -1);
+}
+
+int odl_areas_tracked(odl_areas_tracker* t, const char* nodes_nl, uint32_t n, uint32_t* order,
+                      uint32_t* nh_words, uint32_t* metric, uint32_t* count, uint32_t* links,
+                      uint32_t* need, uint32_t* best, uint32_t* areas_mask, uint32_t* const* nh,
+                      uint8_t* installed) {
+  if (!t) return -1;
+  return guard(t->first, [&]() -> int {
+    // without outputs: the areas' order and words only (what sizes nh)
+    const bool query = !metric && !count && !links && !need && !best && !areas_mask && !nh && !installed;
+    const auto r = t->t->tracked(query ? std::vector<std::string>{} : splitNl(nodes_nl ? nodes_nl : "", n));
+    if (order) std::copy(r.order.begin(), r.order.end(), order);
+    if (nh_words) std::copy(r.words.begin(), r.words.end(), nh_words);
+    auto give = [](const std::vector<uint32_t>& src, uint32_t* dst) {
+      if (dst) std::copy(src.begin(), src.end(), dst);
+    };
+    give(r.metric, metric);
+    give(r.count, count);
+    give(r.links, links);
+    give(r.need, need);
+    give(r.best, best);
+    give(r.areas, areas_mask);
+    if (installed) std::copy(r.installed.begin(), r.installed.end(), installed);
+    if (nh)
+      for (size_t i = 0; i < r.nh.size(); ++i) give(r.nh[i], nh[i]);
+    return 0;
+  }, -1);
+}
+
 
 int odl_track_select(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes, int use_link_metric) {
   return guard(h, [&]() -> int {

@@ -867,6 +867,7 @@ void LinkState::onEngineError(const std::exception& e) {
   // device that cannot give it back: the next selectDelta reports `full`)
   trackPull();
   trackDropDev();
+  for (AreasTracker* t : areasTrackers_) t->pull();  // their baseline leaves with the engine too
   dropSweep();
   if (multi_) ospf_multi_close(multi_);
   else if (engine_) ospf_close(engine_);
@@ -1290,9 +1291,16 @@ uint32_t LinkState::clampedMinNexthop(const SelectAttr& a) {
 }
 
 // ---------------------------------------------------------------- select across areas
-LinkState::AreasResult LinkState::allAreasSelect(const std::vector<LinkState*>& given,
-                                                 const std::vector<std::vector<AreaEntry>>& prefixes,
-                                                 bool useLinkMetric) {
+// the areas by name and the engine's table, as allAreasSelect maps them
+struct LinkState::AreasMap {
+  std::vector<LinkState*> ar;
+  std::vector<std::vector<uint32_t>> gid;
+  std::vector<uint32_t> off, tnode, tarea, tpref, tmnh;
+};
+
+LinkState::AreasResult LinkState::allAreasSelectImpl(
+    const std::vector<LinkState*>& given, const std::vector<std::vector<AreaEntry>>& prefixes,
+    bool useLinkMetric, AreasWhat what, AreasMap* map) {
   if (given.empty() || given.size() > 32)
     throw std::invalid_argument("allAreasSelect: 1 .. 32 areas");
   // the areas by name
@@ -1363,11 +1371,20 @@ LinkState::AreasResult LinkState::allAreasSelect(const std::vector<LinkState*>& 
   }
   out.prefixes = (uint32_t)P;
   out.words.resize(A);
-  out.nh.resize(A);
-  for (size_t a = 0; a < A; ++a) {
-    out.words[a] = ar[a]->selectWords();
-    out.nh[a].assign(ar[a]->csr_->names.size() * P * out.words[a], 0);
+  for (size_t a = 0; a < A; ++a) out.words[a] = ar[a]->selectWords();
+  if (map) {
+    map->ar = ar;
+    map->gid = gid;
+    map->off = off;
+    map->tnode = tnode;
+    map->tarea = tarea;
+    map->tpref = tpref;
+    map->tmnh = tmnh;
   }
+  if (what == AreasWhat::kMapOnly) return out;
+  out.nh.resize(A);
+  for (size_t a = 0; a < A; ++a)
+    out.nh[a].assign(ar[a]->csr_->names.size() * P * out.words[a], 0);
   out.metric.assign(G * P, kInf);
   out.best.assign(G * P, kInf);
   for (auto* v : {&out.count, &out.links, &out.need, &out.areas}) v->assign(G * P, 0);
@@ -1383,12 +1400,12 @@ LinkState::AreasResult LinkState::allAreasSelect(const std::vector<LinkState*>& 
         return false;
     return true;
   };
-  if (deviceOk()) {
+  if (what == AreasWhat::kAny && deviceOk()) {
     // re-sweep the areas whose version moved (a device error there degrades
     // that area: the host path below then answers)
     for (LinkState* ls : ar) ls->prefetchAllSources(useLinkMetric);
   }
-  if (deviceOk()) {
+  if (what == AreasWhat::kAny && deviceOk()) {
     bool swept = true;
     for (LinkState* ls : ar) swept = swept && ls->sweep_ && ls->sweepHas(useLinkMetric);
     if (swept) {
@@ -1540,6 +1557,344 @@ LinkState::AreasResult LinkState::allAreasSelect(const std::vector<LinkState*>& 
   }
   install();
   return out;
+}
+
+
+// ---------------------------------------------------------------- the areas tracker
+LinkState::AreasResult LinkState::allAreasSelect(const std::vector<LinkState*>& given,
+                                                 const std::vector<std::vector<AreaEntry>>& prefixes,
+                                                 bool useLinkMetric) {
+  return allAreasSelectImpl(given, prefixes, useLinkMetric, AreasWhat::kAny, nullptr);
+}
+
+std::unique_ptr<LinkState::AreasTracker> LinkState::trackAreasSelect(
+    const std::vector<LinkState*>& areas, const std::vector<std::vector<AreaEntry>>& prefixes,
+    bool useLinkMetric) {
+  return std::make_unique<AreasTracker>(areas, prefixes, useLinkMetric);
+}
+
+LinkState::AreasTracker::AreasTracker(const std::vector<LinkState*>& areas,
+                                      const std::vector<std::vector<AreaEntry>>& prefixes,
+                                      bool useLinkMetric)
+    : given_(areas), prefixes_(prefixes), ulm_(useLinkMetric) {
+  baseline();  // throws on a bad argument: nothing registered yet
+  for (LinkState* ls : given_) ls->areasTrackers_.push_back(this);
+}
+
+LinkState::AreasTracker::~AreasTracker() {
+  for (LinkState* ls : given_) {
+    auto& l = ls->areasTrackers_;
+    l.erase(std::remove(l.begin(), l.end(), this), l.end());
+  }
+  if (st_) ospf_areastate_destroy(st_);
+}
+
+void LinkState::AreasTracker::remember(const AreasMap& m, const AreasResult& r) {
+  names_ = r.names;
+  order_ = r.order;
+  words_ = r.words;
+  gid_ = m.gid;
+  const size_t A = m.ar.size();
+  areaNames_.resize(A);
+  nbrs_.resize(A);
+  for (size_t a = 0; a < A; ++a) {
+    areaNames_[a] = m.ar[a]->csr_->names;
+    nbrs_[a].resize(areaNames_[a].size());
+    for (uint32_t r0 = 0; r0 < nbrs_[a].size(); ++r0) nbrs_[a][r0] = m.ar[a]->nbrsOf(r0);
+  }
+}
+
+bool LinkState::AreasTracker::namesMoved(const AreasMap& m) const {
+  if (areaNames_.size() != m.ar.size()) return true;
+  for (size_t a = 0; a < m.ar.size(); ++a)
+    if (areaNames_[a] != m.ar[a]->csr_->names) return true;
+  return false;
+}
+
+std::vector<ospf_sweep*> LinkState::AreasTracker::sweeps(const AreasMap& m) {
+  auto deviceOk = [&] {
+    for (LinkState* ls : m.ar)
+      if (ls->hostRun(ulm_) || ls->devices_.size() > 1 || ls->device_ != m.ar[0]->device_)
+        return false;
+    return true;
+  };
+  std::vector<ospf_sweep*> sw;
+  if (!deviceOk()) return sw;
+  for (LinkState* ls : m.ar) ls->prefetchAllSources(ulm_);  // an error there degrades that area
+  if (!deviceOk()) return sw;
+  for (LinkState* ls : m.ar) {
+    if (!ls->sweep_ || !ls->sweepHas(ulm_)) return {};
+    sw.push_back(ls->sweep_);
+  }
+  return sw;
+}
+
+void LinkState::AreasTracker::engineFailed(const AreasMap& m, int rc, const std::string& msg) {
+  // allAreasSelect's rule: a device error degrades every area or, when one may
+  // not degrade, none and the error is thrown; another refusal sends only
+  // this call to the host
+  if (rc != OSPF_E_DEVICE && rc != OSPF_E_NOMEM) return;
+  const EngineError err(rc, msg);
+  for (LinkState* ls : m.ar)
+    if (!ls->degradeOnError_ || !ls->engineOpened_) throw err;
+  for (LinkState* ls : m.ar) ls->onEngineError(err);
+}
+
+void LinkState::AreasTracker::pull() {
+  if (!st_) return;
+  ospf_areastate* st = st_;
+  st_ = nullptr;
+  const size_t A = gid_.size(), G = names_.size(), P = prefixes_.size();
+  AreasResult r;
+  r.order = order_;
+  r.names = names_;
+  r.prefixes = (uint32_t)P;
+  r.words = words_;
+  for (auto* v : {&r.metric, &r.count, &r.links, &r.need, &r.best, &r.areas}) v->assign(G * P, 0);
+  std::vector<std::vector<uint32_t>> byg(A);
+  std::vector<uint32_t*> nhp;
+  for (size_t a = 0; a < A; ++a) {
+    byg[a].assign(G * P * words_[a], 0);
+    nhp.push_back(byg[a].data());
+  }
+  std::vector<uint32_t> roots(G);
+  for (uint32_t g = 0; g < G; ++g) roots[g] = g;
+  const ospf_areas_pout o{r.metric.data(), r.count.data(), r.links.data(), r.need.data(),
+                          r.best.data(),   r.areas.data(), nhp.data(),     words_.data()};
+  const int rc = ospf_areastate_copy(st, roots.data(), (uint32_t)G, &o);
+  ospf_areastate_destroy(st);
+  hostOk_ = rc == OSPF_OK;
+  if (!hostOk_) return;  // the baseline is lost: the next delta is `full`
+  r.nh.resize(A);
+  for (size_t a = 0; a < A; ++a) {
+    const size_t row = P * words_[a];
+    r.nh[a].assign(gid_[a].size() * row, 0);
+    for (size_t i = 0; i < gid_[a].size(); ++i)
+      std::copy(byg[a].begin() + gid_[a][i] * row, byg[a].begin() + (gid_[a][i] + 1) * row,
+                r.nh[a].begin() + i * row);
+  }
+  r.installed.assign(G * P, 0);
+  for (size_t i = 0; i < G * P; ++i) r.installed[i] = r.links[i] > 0 && r.need[i] <= r.links[i];
+  host_ = std::move(r);
+}
+
+void LinkState::AreasTracker::baseline() {
+  if (st_) ospf_areastate_destroy(st_);
+  st_ = nullptr;
+  hostOk_ = false;
+  AreasMap m;
+  const AreasResult r = allAreasSelectImpl(given_, prefixes_, ulm_, AreasWhat::kMapOnly, &m);
+  const std::vector<ospf_sweep*> sw = sweeps(m);
+  if (!sw.empty()) {
+    std::vector<const uint32_t*> gp;
+    for (const auto& g : m.gid) gp.push_back(g.data());
+    const ospf_areas_table t{(uint32_t)sw.size(),      sw.data(),       gp.data(),
+                             (uint32_t)r.names.size(), r.prefixes,      m.off.data(),
+                             m.tnode.data(),           m.tarea.data(),  m.tpref.data(),
+                             m.tmnh.data()};
+    ospf_areastate* st = nullptr;
+    int rc = ospf_areastate_create(&t, &st);
+    std::string msg = "ospf_areastate_create";
+    if (rc == OSPF_OK && (rc = ospf_areastate_prime(st, sw.data())) != OSPF_OK) {
+      msg = ospf_areastate_last_error(st);
+      ospf_areastate_destroy(st);
+    }
+    if (rc == OSPF_OK) {
+      st_ = st;
+      remember(m, r);
+      attrsMoved_ = false;
+      return;
+    }
+    engineFailed(m, rc, msg);
+  }
+  host_ = allAreasSelectImpl(given_, prefixes_, ulm_, AreasWhat::kHostOnly, &m);
+  hostOk_ = true;
+  remember(m, host_);
+  attrsMoved_ = false;
+}
+
+void LinkState::AreasTracker::setAttrs(const std::vector<std::vector<AreaEntry>>& prefixes) {
+  if (prefixes.size() != prefixes_.size())
+    throw std::invalid_argument("setAttrs: another number of prefixes than the tracked table");
+  for (size_t p = 0; p < prefixes.size(); ++p) {
+    if (prefixes[p].size() != prefixes_[p].size())
+      throw std::invalid_argument("setAttrs: another number of entries than the tracked prefix");
+    for (size_t i = 0; i < prefixes[p].size(); ++i)
+      if (prefixes[p][i].node != prefixes_[p][i].node || prefixes[p][i].area != prefixes_[p][i].area)
+        throw std::invalid_argument("setAttrs: the (node, area) entries differ from the tracked table");
+  }
+  prefixes_ = prefixes;
+  attrsMoved_ = true;  // the device columns are replaced by the next delta()
+}
+
+void LinkState::AreasTracker::hostDiff(const AreasResult& now, const AreasMap& m, Delta& d) const {
+  const AreasResult& old = host_;
+  const size_t A = m.ar.size(), G = now.names.size(), P = now.prefixes;
+  uint32_t sumW = 0;
+  for (uint32_t w : now.words) sumW += w;
+  std::vector<uint32_t> row(sumW);
+  for (uint32_t g = 0; g < G; ++g) {
+    // the root's id in each of its areas; rebased when a neighbour list moved
+    std::vector<uint32_t> la(A, kInf);
+    bool reb = false;
+    for (size_t a = 0; a < A; ++a) {
+      const auto it = std::lower_bound(m.gid[a].begin(), m.gid[a].end(), g);
+      if (it == m.gid[a].end() || *it != g) continue;
+      la[a] = (uint32_t)(it - m.gid[a].begin());
+      reb = reb || nbrs_[a][la[a]] != m.ar[a]->nbrsOf(la[a]);
+    }
+    if (reb) {
+      d.rebased.push_back(g);
+      continue;
+    }
+    for (size_t p = 0; p < P; ++p) {
+      const size_t c = (size_t)g * P + p;
+      bool ch = old.metric[c] != now.metric[c] || old.count[c] != now.count[c] ||
+                old.links[c] != now.links[c] || old.need[c] != now.need[c] ||
+                old.best[c] != now.best[c] || old.areas[c] != now.areas[c];
+      std::fill(row.begin(), row.end(), 0u);
+      uint32_t base = 0;
+      for (size_t a = 0; a < A; ++a) {
+        const uint32_t Wn = now.words[a], Wo = old.words[a];
+        if (la[a] != kInf) {
+          const uint32_t* n = now.nh[a].data() + ((size_t)la[a] * P + p) * Wn;
+          const uint32_t* o = old.nh[a].data() + ((size_t)la[a] * P + p) * Wo;
+          for (uint32_t w = 0; w < std::max(Wn, Wo); ++w) {
+            const uint32_t x = w < Wn ? n[w] : 0u, y = w < Wo ? o[w] : 0u;
+            ch = ch || x != y;
+            if (w < Wn) row[base + w] = x;
+          }
+        }
+        base += Wn;
+      }
+      if (!ch) continue;
+      d.changes.push_back(AreasChange{g, (uint32_t)p, now.metric[c], now.count[c], now.links[c],
+                                      now.need[c], now.best[c], now.areas[c]});
+      d.nh.insert(d.nh.end(), row.begin(), row.end());
+    }
+  }
+}
+
+LinkState::AreasTracker::Delta LinkState::AreasTracker::delta() {
+  Delta d;
+  AreasMap m;
+  const AreasResult r = allAreasSelectImpl(given_, prefixes_, ulm_, AreasWhat::kMapOnly, &m);
+  d.words = r.words;
+  auto finish = [&] {
+    d.installed.resize(d.changes.size());
+    for (size_t i = 0; i < d.changes.size(); ++i)
+      d.installed[i] = d.changes[i].links > 0 && d.changes[i].need <= d.changes[i].links;
+  };
+  if (namesMoved(m) || (!st_ && !hostOk_)) {
+    baseline();
+    d.words = words_;
+    d.full = true;
+    d.onDevice = st_ != nullptr;
+    return d;
+  }
+  if (st_) {
+    const std::vector<ospf_sweep*> sw = sweeps(m);  // may pull the baseline (an area's own error)
+    if (st_ && !sw.empty()) {
+      int rc = OSPF_OK;
+      if (attrsMoved_) rc = ospf_areastate_set_policy(st_, m.tpref.data(), m.tmnh.data());
+      if (rc == OSPF_OK) {
+        attrsMoved_ = false;
+        uint32_t sumW = 0;
+        for (uint32_t w : r.words) sumW += w;
+        static_assert(sizeof(AreasChange) == sizeof(ospf_areas_change), "records are the engine's");
+        for (;;) {
+          d.changes.resize(cap_);
+          d.nh.resize((size_t)cap_ * sumW);
+          d.rebased.resize(capReb_);
+          uint32_t n = 0, nr = 0;
+          rc = ospf_areastate_update(st_, sw.data(), r.words.data(),
+                                     reinterpret_cast<ospf_areas_change*>(d.changes.data()),
+                                     d.nh.data(), cap_, &n, d.rebased.data(), capReb_, &nr);
+          if (rc == OSPF_E_RANGE && (n > cap_ || nr > capReb_)) {  // the lists did not fit: grow
+            cap_ = std::max(cap_, n);
+            capReb_ = std::max(capReb_, nr);
+            continue;
+          }
+          d.changes.resize(rc == OSPF_OK ? n : 0);
+          d.nh.resize(rc == OSPF_OK ? (size_t)n * sumW : 0);
+          d.rebased.resize(rc == OSPF_OK ? nr : 0);
+          break;
+        }
+        if (rc == OSPF_OK) {
+          d.onDevice = true;
+          remember(m, r);
+          finish();
+          return d;
+        }
+      }
+      const std::string msg = ospf_areastate_last_error(st_);
+      pull();  // the previous result off the device before any engine goes
+      engineFailed(m, rc, msg);
+    }
+    pull();
+    if (!hostOk_) {
+      baseline();
+      d = Delta{};
+      d.words = words_;
+      d.full = true;
+      d.onDevice = st_ != nullptr;
+      return d;
+    }
+  }
+  AreasResult now = allAreasSelectImpl(given_, prefixes_, ulm_, AreasWhat::kHostOnly, &m);
+  d.words = now.words;
+  hostDiff(now, m, d);
+  host_ = std::move(now);
+  remember(m, host_);
+  attrsMoved_ = false;
+  finish();
+  return d;
+}
+
+LinkState::AreasResult LinkState::AreasTracker::tracked(const std::vector<std::string>& nodes) {
+  if (!st_ && !hostOk_) throw std::logic_error("AreasTracker::tracked: the baseline was lost (delta)");
+  const size_t A = gid_.size(), P = prefixes_.size(), n = nodes.size();
+  std::vector<uint32_t> ids;
+  for (const auto& nm : nodes) {
+    const auto it = std::lower_bound(names_.begin(), names_.end(), nm);
+    if (it == names_.end() || *it != nm) throw std::invalid_argument("AreasTracker::tracked: unknown node " + nm);
+    ids.push_back((uint32_t)(it - names_.begin()));
+  }
+  AreasResult r;
+  r.order = order_;
+  r.names = nodes;
+  r.prefixes = (uint32_t)P;
+  r.words = words_;
+  for (auto* v : {&r.metric, &r.count, &r.links, &r.need, &r.best, &r.areas}) v->assign(n * P, 0);
+  r.nh.resize(A);
+  for (size_t a = 0; a < A; ++a) r.nh[a].assign(n * P * words_[a], 0);
+  if (st_) {
+    std::vector<uint32_t*> nhp;
+    for (size_t a = 0; a < A; ++a) nhp.push_back(r.nh[a].data());
+    const ospf_areas_pout o{r.metric.data(), r.count.data(), r.links.data(), r.need.data(),
+                            r.best.data(),   r.areas.data(), nhp.data(),     words_.data()};
+    if (const int rc = ospf_areastate_copy(st_, ids.data(), (uint32_t)n, &o))
+      throw EngineError(rc, ospf_areastate_last_error(st_));
+    r.onDevice = true;
+  } else {
+    for (size_t i = 0; i < n; ++i) {
+      const uint32_t g = ids[i];
+      for (auto [dst, src] : {std::pair{&r.metric, &host_.metric}, {&r.count, &host_.count},
+                              {&r.links, &host_.links}, {&r.need, &host_.need},
+                              {&r.best, &host_.best}, {&r.areas, &host_.areas}})
+        std::copy(src->begin() + (size_t)g * P, src->begin() + (size_t)(g + 1) * P, dst->begin() + i * P);
+      for (size_t a = 0; a < A; ++a) {
+        const auto it = std::lower_bound(gid_[a].begin(), gid_[a].end(), g);
+        if (it == gid_[a].end() || *it != g) continue;
+        const size_t row = P * host_.words[a], la = it - gid_[a].begin();
+        std::copy(host_.nh[a].begin() + la * row, host_.nh[a].begin() + (la + 1) * row,
+                  r.nh[a].begin() + i * row);
+      }
+    }
+  }
+  r.installed.assign(n * P, 0);
+  for (size_t i = 0; i < n * P; ++i) r.installed[i] = r.links[i] > 0 && r.need[i] <= r.links[i];
+  return r;
 }
 
 LinkState::PolicyResult LinkState::allSourcesSelect(

@@ -608,9 +608,9 @@ class LinkState {
   // area (they share the device; all of them or, when one may not degrade,
   // none and the error is thrown); any other engine refusal (contract, LDS
   // size) sends only this call to the host.
-  // Not covered: a resident multi-area state and its delta, UCMP across
-  // areas, SR_MPLS per-destination next hops and KSP2, BGP metric vectors,
-  // several devices.
+  // The same selection kept resident and its delta: AreasTracker below.
+  // Not covered: UCMP across areas, SR_MPLS per-destination next hops and
+  // KSP2, BGP metric vectors, several devices.
   struct AreaEntry {
     std::string node, area;
     SelectAttr attr;
@@ -628,6 +628,79 @@ class LinkState {
   static AreasResult allAreasSelect(const std::vector<LinkState*>& areas,
                                     const std::vector<std::vector<AreaEntry>>& prefixes,
                                     bool useLinkMetric = true);
+  // Only the cells of allAreasSelect's route DB an event in some area (or a
+  // change of the entries' attributes) altered: calculateUpdate
+  // (SpfSolver.cpp:24-59) across areas. A tracker is bound to the given
+  // LinkStates (which must outlive it) and one table, mapped as allAreasSelect
+  // maps it; its baseline is an ospf_areastate primed from the areas' sweeps,
+  // or -- when an area is in host mode, multi-device, on another device or
+  // degraded, or when the engine call fails (allAreasSelect's rule for who
+  // degrades) -- the previous AreasResult kept on the host and diffed against
+  // a fresh host-path one. Before an engine goes (a device error in any of the
+  // areas) the baseline is copied off the device (ospf_areastate_copy), so a
+  // degraded call still answers the delta.
+  //   delta()    sweeps again every area whose version moved and returns the
+  //              changed cells (records with the NEW values; nh: per record
+  //              the areas' words one after the other, area a's words[a] of
+  //              them) and the rebased global roots; capacities grow on
+  //              OSPF_E_RANGE. `full`: the node-name set of an area changed
+  //              (global ids or a gid moved): a new baseline is made, no lists.
+  //   tracked()  the committed cells of some global nodes: the columns
+  //              [n][prefixes], nh[a] [n][prefixes][words[a]] in `nodes` order
+  //              (zero where the area does not hold the node).
+  //   setAttrs() the same (node, area) entries with new attributes, applied by
+  //              the next delta() (ospf_areastate_set_policy); a change made
+  //              while the name set differs goes into the new baseline.
+  struct AreasChange {
+    uint32_t root, prefix, metric, count, links, need, best, areas;
+  };
+  struct AreasMap;
+  class AreasTracker {
+   public:
+    struct Delta {
+      std::vector<uint32_t> words;  // per area (name order)
+      std::vector<AreasChange> changes;
+      std::vector<uint32_t> nh;       // [changes][sum of words]
+      std::vector<uint32_t> rebased;  // global ids
+      std::vector<uint8_t> installed;  // per change
+      bool full = false, onDevice = false;
+    };
+    AreasTracker(const std::vector<LinkState*>& areas,
+                 const std::vector<std::vector<AreaEntry>>& prefixes, bool useLinkMetric);
+    ~AreasTracker();
+    AreasTracker(const AreasTracker&) = delete;
+    AreasTracker& operator=(const AreasTracker&) = delete;
+    Delta delta();
+    AreasResult tracked(const std::vector<std::string>& nodes);
+    void setAttrs(const std::vector<std::vector<AreaEntry>>& prefixes);
+    const std::vector<std::vector<AreaEntry>>& prefixes() const { return prefixes_; }
+    // the device baseline onto the host (before an area's engine goes)
+    void pull();
+
+   private:
+    void baseline();
+    void remember(const AreasMap& m, const AreasResult& r);
+    bool namesMoved(const AreasMap& m) const;
+    std::vector<ospf_sweep*> sweeps(const AreasMap& m);
+    void engineFailed(const AreasMap& m, int rc, const std::string& msg);
+    void hostDiff(const AreasResult& now, const AreasMap& m, Delta& d) const;
+    std::vector<LinkState*> given_;
+    std::vector<std::vector<AreaEntry>> prefixes_;
+    bool ulm_ = true, attrsMoved_ = false, hostOk_ = false;
+    struct ospf_areastate* st_ = nullptr;
+    AreasResult host_;  // the baseline when st_ is null
+    // of the committed baseline: the global names, per area (name order) the
+    // node names, global ids, words and every node's distinct neighbours
+    std::vector<std::string> names_;
+    std::vector<std::vector<std::string>> areaNames_;
+    std::vector<std::vector<uint32_t>> gid_;
+    std::vector<uint32_t> words_, order_;
+    std::vector<std::vector<std::vector<uint32_t>>> nbrs_;
+    uint32_t cap_ = 1024, capReb_ = 64;
+  };
+  static std::unique_ptr<AreasTracker> trackAreasSelect(
+      const std::vector<LinkState*>& areas, const std::vector<std::vector<AreaEntry>>& prefixes,
+      bool useLinkMetric = true);
   // Only the selections a topology change altered: the counterpart of
   // DecisionRouteDb::calculateUpdate (SpfSolver.cpp:24-59) for
   // allSourcesSelect's route DB. trackSelect binds the LinkState to one
@@ -963,6 +1036,15 @@ class LinkState {
   // clamped threshold (policyTable's, shared with allAreasSelect)
   static std::vector<uint32_t> classRanks(const std::vector<SelectAttr>& attrs);
   static uint32_t clampedMinNexthop(const SelectAttr& a);
+  // allAreasSelect's steps: as the public call (the device, else the host),
+  // on the host path only, or the mapping only (order, names, words; no cell
+  // computed or allocated); `map` (may be null) receives the areas by name
+  // and the engine's table
+  enum class AreasWhat { kAny, kHostOnly, kMapOnly };
+  static AreasResult allAreasSelectImpl(const std::vector<LinkState*>& areas,
+                                        const std::vector<std::vector<AreaEntry>>& prefixes,
+                                        bool useLinkMetric, AreasWhat what, AreasMap* map);
+  std::vector<AreasTracker*> areasTrackers_;  // the trackers over this area
   // ---- trackSelect ----
   bool tracking_ = false, trackMetric_ = true;
   bool trackPolicy_ = false;       // tracked with attributes: the policy selection

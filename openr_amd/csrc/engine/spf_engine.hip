@@ -1446,6 +1446,9 @@ int ospf_close(ospf_ctx* c) {
   for (ospf_selstate* st : std::vector<ospf_selstate*>(c->live_selstates))
     if (c->release_selstate) c->release_selstate(st);
   c->live_selstates.clear();
+  for (ospf_areastate* st : std::vector<ospf_areastate*>(c->live_areastates))
+    if (c->release_areastate) c->release_areastate(st);
+  c->live_areastates.clear();
   if (c->d_graph) hipFree(c->d_graph);
   for (auto& kv : c->scratch)
     if (kv.second.p) hipFree(kv.second.p);

@@ -42,6 +42,10 @@ struct ospf_ctx {
   // they outlive the sweeps of one graph version)
   std::vector<struct ospf_selstate*> live_selstates;
   void (*release_selstate)(struct ospf_selstate*) = nullptr;
+  // and for the multi-area states (ospf_areastate_*): a state is listed on
+  // each of its areas' contexts; the first one closed releases it
+  std::vector<struct ospf_areastate*> live_areastates;
+  void (*release_areastate)(struct ospf_areastate*) = nullptr;
   // graph
   bool loaded = false;
   ospf_graph_info info{};

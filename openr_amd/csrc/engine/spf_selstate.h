@@ -1,7 +1,9 @@
 // spf_selstate.h — the select state and what its translation units share:
 // spf_seldelta.hip (the resident selection, prime / update / copy),
 // spf_seldelta_policy.hip (the same under the best-route policy) and
-// spf_ucmp.hip (the UCMP weights resolved over either). Not a public header.
+// spf_ucmp.hip (the UCMP weights resolved over either), and what
+// spf_selareas.hip shares with the multi-area state of spf_seldelta_areas.hip.
+// Not a public header.
 #pragma once
 
 #include <algorithm>
@@ -58,7 +60,9 @@ struct ospf_selstate {
 namespace ospf_int {
 namespace selst {
 
-inline int stfail(ospf_selstate* st, int code, const std::string& m) {
+// `St`: ospf_selstate or ospf_areastate (c, err, device_bytes)
+template <class St>
+inline int stfail(St* st, int code, const std::string& m) {
   st->err = m;
   if (st->c) st->c->err = m;
   return code;
@@ -72,15 +76,16 @@ inline int stfail(ospf_selstate* st, int code, const std::string& m) {
                                      std::string(#call) + ": " + hipGetErrorString(e_));   \
   } while (0)
 
-inline void dfree(ospf_selstate* st, void* p, size_t bytes) {
+template <class St>
+inline void dfree(St* st, void* p, size_t bytes) {
   if (!p) return;
   (void)hipFree(p);
   st->device_bytes -= std::min<uint64_t>(st->device_bytes, bytes);
 }
 
 // *p grown to `count` elements (contents dropped); `have` = its capacity
-template <class T>
-int grow(ospf_selstate* st, T** p, size_t* have, size_t count) {
+template <class St, class T>
+int grow(St* st, T** p, size_t* have, size_t count) {
   count = std::max<size_t>(count, 1);
   if (*p && *have >= count) return OSPF_OK;
   dfree(st, *p, *have * sizeof(T));
@@ -116,6 +121,18 @@ uint32_t max_words(const ospf_sweep* sw);
 // are in place): queued on the null stream, not waited for
 int policy_delta_launch(ospf_selstate* st, ospf_sweep* sw, bool compare, uint32_t nh_words,
                         bool want_nh, uint32_t cap, uint32_t cap_reb);
+
+// ---- spf_selareas.hip
+// ospf_areas_select_policy's per-sweep rules for `s` beside area 0's sweep s0
+// (null: they hold)
+const char* areas_sweep_error(const ospf_sweep* s, const ospf_sweep* s0);
+// the gid lists and the table of `t` against areas of Va[a] nodes (t->sweeps is
+// not read): null when they hold, else what is wrong. Fills lid [A][G] (global
+// -> node id) on the way.
+const char* areas_table_error(const ospf_areas_table* t, const uint32_t* Va,
+                              std::vector<uint32_t>& lid);
+// every node's rows of a sweep that owns every root, by node id (s->d_area_rows)
+int area_rows(ospf_sweep* s);
 
 }  // namespace selst
 }  // namespace ospf_int

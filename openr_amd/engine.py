@@ -815,6 +815,128 @@ class SelState:
             return adv, status, off, wt[: int(need.value)]
 
 
+# ospf_areas_change records, with the derived `installed` column
+ACHANGE_DTYPE = np.dtype([(k, np.uint32) for k in ("root", "prefix", "metric", "count", "links",
+                                                   "need", "best", "areas")])
+ACHANGE_OUT_DTYPE = np.dtype(ACHANGE_DTYPE.descr + [("installed", np.uint32)])
+
+
+class AreaSelState:
+    """ospf_areastate: select_policy_areas' selection of one table of (global
+    node, area) entries for every node of the union of the areas, kept on the
+    device in each root's own widths, and the cells a later sweep of some areas
+    (or a change of the attributes) changed. Bound to the areas' Engines (the
+    sweeps are read for them and their node counts only) and to one table.
+    Roots are global ids."""
+
+    def __init__(self, sweeps: Sequence["Sweep"], gids: Sequence[Sequence[int]], n_global: int,
+                 offsets: Sequence[int], node: Sequence[int], area: Sequence[int],
+                 pref: Optional[Sequence[int]], min_nexthop: Optional[Sequence[int]] = None):
+        self._L = N.engine()
+        t, keep = areas_table(sweeps, gids, n_global, offsets, node, area, pref, min_nexthop)
+        h = C.c_void_p()
+        rc = self._L.ospf_areastate_create(C.byref(t), C.byref(h))
+        if rc != 0:
+            s = sweeps[0] if len(sweeps) else None
+            raise EngineError(rc, "" if s is None else
+                              self._L.ospf_last_error(s.engine._h).decode())
+        self.A, self.G, self.P = len(sweeps), int(n_global), int(t.n_prefixes)
+        self.n_entries = 0 if keep[4][0] is None else int(keep[4][0].size)
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ospf_areastate_destroy(self._h)
+        self._h = None
+
+    __del__ = close
+
+    def _msg(self) -> str:
+        return self._L.ospf_areastate_last_error(self._h).decode()
+
+    def _sweeps(self, sweeps):
+        if len(sweeps) != self.A:
+            raise ValueError("one sweep per area of the state")
+        return (C.c_void_p * max(1, self.A))(*[None if s is None else s._h for s in sweeps])
+
+    def device_bytes(self) -> int:
+        return int(self._L.ospf_areastate_device_bytes(self._h))
+
+    def prime(self, sweeps: Sequence["Sweep"]) -> None:
+        """Store the sweeps' selection as the baseline; reports nothing."""
+        rc = self._L.ospf_areastate_prime(self._h, self._sweeps(sweeps))
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+
+    def update(self, sweeps: Sequence["Sweep"], cap: int = 1024, cap_rebased: int = 64,
+               nh_words: Optional[Sequence[int]] = None):
+        """ospf_areastate_update: compare the sweeps' selection with the stored
+        one and commit it -> (records [n] structured u32 root / prefix / metric
+        / count / links / need / best / areas / installed with the NEW values,
+        nh [n, sum(nh_words)] u32 with area a's words from column
+        sum(nh_words[:a]), rebased roots [m] u32). Raises SelStateOverflow
+        (code -4, n_changes / n_rebased attached, state unchanged) when a list
+        does not fit its capacity."""
+        if cap < 0 or cap_rebased < 0:
+            raise ValueError("capacities must be >= 0")
+        W = np.ascontiguousarray(
+            nh_words if nh_words is not None else [max(1, s.max_nh_words) for s in sweeps],
+            np.uint32)
+        if W.size != self.A:
+            raise ValueError("one nh_words per area")
+        rec = np.zeros(max(1, cap), ACHANGE_DTYPE)
+        nh = np.zeros((max(1, cap), int(W.sum())), np.uint32)
+        reb = np.zeros(max(1, cap_rebased), np.uint32)
+        n, m = C.c_uint32(), C.c_uint32()
+        rc = self._L.ospf_areastate_update(self._h, self._sweeps(sweeps), W.ctypes.data,
+                                           rec.ctypes.data, nh.ctypes.data, cap, C.byref(n),
+                                           reb.ctypes.data, cap_rebased, C.byref(m))
+        if rc == -4:
+            raise SelStateOverflow(self._msg(), int(n.value), int(m.value))
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+        out = np.zeros(n.value, ACHANGE_OUT_DTYPE)
+        for k in ACHANGE_DTYPE.names:
+            out[k] = rec[k][: n.value]
+        out["installed"] = (out["links"] > 0) & (out["need"] <= out["links"])
+        return out, nh[: n.value], reb[: m.value]
+
+    def copy(self, roots: Sequence[int], nh_words: Sequence[int]) -> Dict[str, object]:
+        """ospf_areastate_copy: the committed cells of `roots` (global ids) ->
+        select_policy_areas' keys, rows in `roots` order: the six columns
+        [n, P], nh a list of [n, P, nh_words[a]] (zero where the area does not
+        hold the root)."""
+        roots = np.ascontiguousarray(roots, np.uint32)
+        W = np.ascontiguousarray(nh_words, np.uint32)
+        if W.size != self.A:
+            raise ValueError("one nh_words per area")
+        n = int(roots.size)
+        out: Dict[str, object] = {k: np.zeros((n, self.P), np.uint32) for k in AREAS_OUTPUTS[:6]}
+        out["nh"] = [np.zeros((n, self.P, int(w)), np.uint32) for w in W]
+        nhp = (C.c_void_p * max(1, self.A))(*[x.ctypes.data for x in out["nh"]])
+        o = N.ospf_areas_pout(*[out[k].ctypes.data for k in AREAS_OUTPUTS[:6]],
+                              C.cast(nhp, C.c_void_p), W.ctypes.data)
+        rc = self._L.ospf_areastate_copy(self._h, roots.ctypes.data, n, C.byref(o))
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+        return out
+
+    def set_policy(self, pref: Optional[Sequence[int]],
+                   min_nexthop: Optional[Sequence[int]] = None) -> None:
+        """ospf_areastate_set_policy: replace the class ranks and thresholds
+        (one per entry). Nothing committed changes; the next update reports
+        what the new attributes changed."""
+        pr = None if pref is None else np.ascontiguousarray(pref, np.uint32)
+        mn = None if min_nexthop is None else np.ascontiguousarray(min_nexthop, np.uint32)
+        for a in (pr, mn):
+            if a is not None and a.size != self.n_entries:
+                raise ValueError("pref / min_nexthop: one per entry")
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+        rc = self._L.ospf_areastate_set_policy(self._h, ptr(pr), ptr(mn))
+        if rc != 0:
+            raise EngineError(rc, self._msg())
+
+
 class Multi:
     """Several devices behind one handle (ospf_multi_*): the graph replicated,
     sweeps partitioned by device slot, digests gathered by peer copies."""

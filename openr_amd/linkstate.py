@@ -279,6 +279,132 @@ def all_areas_select_policy(areas: Sequence["LinkState"], prefixes: Dict[str, Se
     return out
 
 
+def _areas_lines(prefixes):
+    """{prefix: [(node, area, path_pref, source_pref, distance, min_nexthop or
+    None)]} -> (lines of tab-separated name pairs, [n, 4] i64 attributes)"""
+    unset = -(1 << 63)
+    lines, attrs = [], []
+    for ents in prefixes.values():
+        f = []
+        for nm, ar, pp, sp, dist, mn in ents:
+            for x in (nm, ar):
+                if not x or "\n" in x or "\t" in x:
+                    raise ValueError("names must be non-empty, without tabs and newlines")
+            f += [nm, ar]
+            attrs.append((int(pp), int(sp), int(dist), unset if mn is None else int(mn)))
+        lines.append("\t".join(f))
+    return lines, np.ascontiguousarray(attrs, np.int64).reshape(-1, 4)
+
+
+class AreasTracker:
+    """odl::LinkState::AreasTracker: all_areas_select_policy's selection kept
+    resident (on the device: ospf_areastate_*) and only the cells an event in
+    some area or a change of the attributes altered. `areas`: one LinkState per
+    area (kept alive by the tracker); `prefixes` as all_areas_select_policy
+    takes them."""
+
+    def __init__(self, areas: Sequence["LinkState"], prefixes: Dict[str, Sequence[tuple]],
+                 use_link_metric: bool = True):
+        self._L = N.decision()
+        self.areas = list(areas)
+        self._by_name = sorted(self.areas, key=lambda a: a.area.encode())
+        self.area_names = [a.area for a in self._by_name]
+        lines, at = _areas_lines(prefixes)
+        self.P = len(lines)
+        self._entries = [[(e[0], e[1]) for e in ents] for ents in prefixes.values()]
+        A = len(self.areas)
+        hs = (C.c_void_p * max(1, A))(*[a._h for a in self.areas])
+        h = C.c_void_p()
+        if not self.areas or self._L.odl_areas_track(
+                hs, A, "\n".join(lines).encode(), len(lines), at.ctypes.data if at.size else None,
+                at.shape[0], int(use_link_metric), C.byref(h)) != 0:
+            raise LinkStateError(self.areas[0]._err() if self.areas else "no areas")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.odl_areas_untrack(self._h)
+        self._h = None
+
+    __del__ = close
+
+    def _err(self):
+        return self.areas[0]._err()
+
+    def delta(self) -> dict:
+        """odl_areas_delta -> dict(changes = structured array root / prefix /
+        metric / count / links / need / best / areas / installed with the NEW
+        values (root: global id), nh [n, sum(words)] u32 (the areas' words one
+        after the other, areas by name), words per area, rebased global ids,
+        full, on_device)."""
+        from .engine import ACHANGE_DTYPE, ACHANGE_OUT_DTYPE
+        A = len(self.areas)
+        n, m, full, dev = C.c_uint32(), C.c_uint32(), C.c_int32(), C.c_int32()
+        words = np.zeros(max(1, A), np.uint32)
+        pc, pn, pr = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        if self._L.odl_areas_delta(self._h, C.byref(n), C.byref(m), words.ctypes.data,
+                                   C.byref(full), C.byref(dev), C.byref(pc), C.byref(pn),
+                                   C.byref(pr)) != 0:
+            raise LinkStateError(self._err())
+        try:
+            def take(p, count, dtype):
+                if not count:
+                    return np.zeros(0, dtype)
+                nbytes = count * np.dtype(dtype).itemsize
+                return np.frombuffer(C.string_at(p, nbytes), dtype).copy()
+            W = int(words[:A].sum())
+            rec = take(pc, n.value, ACHANGE_DTYPE)
+            nh = take(pn, n.value * W, np.uint32).reshape(n.value, W)
+            rebased = take(pr, m.value, np.uint32)
+        finally:
+            for p in (pc, pn, pr):
+                self._L.odl_free_buf(p)
+        changes = np.zeros(rec.size, ACHANGE_OUT_DTYPE)
+        for k in ACHANGE_DTYPE.names:
+            changes[k] = rec[k]
+        changes["installed"] = (rec["links"] > 0) & (rec["need"] <= rec["links"])
+        return {"changes": changes, "nh": nh, "words": words[:A].copy(), "rebased": rebased,
+                "full": bool(full.value), "on_device": bool(dev.value)}
+
+    def tracked(self, nodes: Sequence[str]) -> dict:
+        """odl_areas_tracked: the committed cells of some global nodes (names)
+        -> metric / count / links / need / best / areas [n, P] u32, nh a list
+        (areas by name) of [n, P, words[a]] u32 in `nodes` order, installed,
+        words, area_names."""
+        A, n, P = len(self.areas), len(nodes), self.P
+        order = np.zeros(max(1, A), np.uint32)
+        words = np.zeros(max(1, A), np.uint32)
+        if self._L.odl_areas_tracked(self._h, b"", 0, order.ctypes.data, words.ctypes.data,
+                                     *([None] * 8)) != 0:
+            raise LinkStateError(self._err())
+        out = {k: np.zeros((n, P), np.uint32)
+               for k in ("metric", "count", "links", "need", "best", "areas")}
+        nh = [np.zeros((n, P, int(w)), np.uint32) for w in words[:A]]
+        nhp = (C.c_void_p * max(1, A))(*[x.ctypes.data for x in nh])
+        inst = np.zeros((n, P), np.uint8)
+        if self._L.odl_areas_tracked(self._h, "\n".join(nodes).encode(), n, order.ctypes.data,
+                                     words.ctypes.data,
+                                     *[out[k].ctypes.data for k in
+                                       ("metric", "count", "links", "need", "best", "areas")],
+                                     nhp, inst.ctypes.data) != 0:
+            raise LinkStateError(self._err())
+        out["nh"] = nh
+        out["installed"] = inst.astype(bool)
+        out["words"] = words[:A].copy()
+        out["area_names"] = list(self.area_names)
+        return out
+
+    def set_policy(self, prefixes: Dict[str, Sequence[tuple]]) -> None:
+        """odl_areas_set_attrs: the same (node, area) entries with new
+        attributes; the next delta() reports what they changed."""
+        if [[(e[0], e[1]) for e in ents] for ents in prefixes.values()] != self._entries:
+            raise ValueError("set_policy: the (node, area) entries differ from the tracked table")
+        _, at = _areas_lines(prefixes)
+        if self._L.odl_areas_set_attrs(self._h, at.ctypes.data if at.size else None,
+                                       at.shape[0]) != 0:
+            raise LinkStateError(self._err())
+
+
 class LinkState:
     """odl::LinkState over the MI355X SPF engine (device `device`)."""
 

@@ -214,14 +214,38 @@ int odl_all_sources_select(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefi
  *   best      [V][n_prefixes]  bestNodeArea's node id, 0xFFFFFFFF when no
  *                              announcer is reached;
  *   installed [V][n_prefixes]  (bytes) 1 iff links > 0 and need <= links.
- * nh_words / *nh_words_needed as above. Not covered: SR_MPLS per-destination
- * next hops, KSP2 and per-area distance selection, BGP metric vectors.
+ * nh_words / *nh_words_needed as above. SR_MPLS per-destination next hops:
+ * odl_all_sources_select_srmpls below. Not covered: KSP2 and per-area distance
+ * selection, BGP metric vectors.
  * Several areas: odl_areas_select_policy. */
 int odl_all_sources_select_policy(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefixes,
                                   const int64_t* attrs, uint32_t n_attrs, int use_link_metric,
                                   uint32_t nh_words, uint32_t* nh_words_needed, uint32_t* metric,
                                   uint32_t* count, uint32_t* nh, uint32_t* links, uint32_t* need,
                                   uint32_t* best, uint8_t* installed);
+/* The same for prefixes forwarded as SR_MPLS (LinkState::allSourcesSelectSrMpls
+ * -> ospf_sweep_select_srmpls on one device, the same rule on the host path:
+ * host mode, several devices, after a device error): the next hops are kept
+ * per destination instead of ORed. Arguments as odl_all_sources_select_policy
+ * with FIVE int64 per announcer name: the fifth is 1 when the entry has a
+ * prepend label, else 0 (a node whose own entry has one routes to the other
+ * announcers, SpfSolver.cpp:794-802). The kept entries of a prefix (unknown
+ * names dropped, the first occurrence of a name, ascending by node id) are
+ * indexed by entry_offsets [n_prefixes + 1]; A = entry_offsets[n_prefixes] is
+ * at most the number of names given, so buffers sized for every name suffice.
+ * Outputs by node id, any may be NULL: metric / count / links / need / best
+ * [V][P], installed [V][P], dst_links [V][A] and dst_nh [V][A][nh_words] in
+ * the kept-entry order. links counts (link, destination) pairs: the route's
+ * nextHops.size() when the node labels are valid and distinct and a prepend
+ * label is valid; the caller builds the PUSH stacks. nh_words 0 returns the
+ * width only. Not covered: the resident selection and its delta, several
+ * areas, KSP2, static MPLS next hops. */
+int odl_all_sources_select_srmpls(odl_ls* ls, const char* prefixes_nl, uint32_t n_prefixes,
+                                  const int64_t* attrs, uint32_t n_attrs, int use_link_metric,
+                                  uint32_t nh_words, uint32_t* nh_words_needed,
+                                  uint32_t* entry_offsets, uint32_t* metric, uint32_t* count,
+                                  uint32_t* links, uint32_t* need, uint32_t* best,
+                                  uint32_t* dst_links, uint32_t* dst_nh, uint8_t* installed);
 /* The same selection across several areas, one LinkState each
  * (LinkState::allAreasSelect -> ospf_areas_select_policy over the areas'
  * resident sweeps, or the same steps on the host over each area's
@@ -244,8 +268,9 @@ int odl_all_sources_select_policy(odl_ls* ls, const char* prefixes_nl, uint32_t 
  * [nh_words[i]] by that area's node id. *on_device: 1 when the device
  * answered. Errors (-1) are reported on areas[0]. The same selection kept
  * resident and its delta: odl_areas_track below. Not covered: UCMP across
- * areas, SR_MPLS per-destination next hops and KSP2, BGP metric vectors,
- * several devices. */
+ * areas, SR_MPLS per-destination next hops across areas (one area:
+ * odl_all_sources_select_srmpls) and KSP2, BGP metric vectors, several
+ * devices. */
 int odl_areas_select_policy(odl_ls* const* areas, uint32_t n_areas, const char* prefixes_nl,
                             uint32_t n_prefixes, const int64_t* attrs, uint32_t n_attrs,
                             int use_link_metric, uint32_t* n_global, uint32_t* order,

@@ -704,7 +704,8 @@ int ospf_sweep_select(ospf_sweep* sw, const ospf_select_table* table, uint32_t n
  * ospf_sweep_select; in addition OSPF_E_INVAL for a pref >= 2^31, a NULL pref
  * (with announcers) and a sweep that does not describe the context's current
  * graph (the kernel reads the live CSR and no-transit bits).
- * Not covered: SR_MPLS per-destination next hops, K_SHORTEST_DISTANCE_2 and
+ * SR_MPLS per-destination next hops: ospf_sweep_select_srmpls below (one area,
+ * one sweep). Not covered: K_SHORTEST_DISTANCE_2 and
  * PER_AREA_SHORTEST_DISTANCE, BGP metric vectors. (Several areas:
  * ospf_areas_select_policy below. The same
  * selection kept resident, its delta and UCMP over it: the policy state of
@@ -725,6 +726,68 @@ int ospf_sweep_select_policy_dev(ospf_sweep* sw, const ospf_select_ptable* table
 /* host outputs, synchronous (after the work queued on every stream) */
 int ospf_sweep_select_policy(ospf_sweep* sw, const ospf_select_ptable* table, uint32_t nh_words,
                              const ospf_select_pout* out);
+/* The same selection for a prefix forwarded as SR_MPLS: selectBestPathsSpf
+ * calls getNextHopsWithMetric(..., perDestination = true) (openr/decision/
+ * SpfSolver.cpp:784-806), so the route is a set of (next hop, destination)
+ * pairs (:1189-1261) and the next hops of the selected announcers are NOT
+ * ORed. Each entry i carries, beside pref and min_nexthop,
+ *   flags[i]        OSPF_SEL_SELF_PREPEND (bit 0): the entry has a prepend
+ *                   label; it matters only on the root's own entry. Any other
+ *                   bit set is OSPF_E_INVAL.
+ * Per (root r, prefix p), with R, S, S', need and best exactly as
+ * ospf_sweep_select_policy defines them (need includes the root's own entry):
+ *   D  = S' without r's own entry when that entry is in S' and has
+ *        OSPF_SEL_SELF_PREPEND (filteredBestNodeAreas, :794-802: an announcing
+ *        root routes to the OTHER announcers); S' otherwise;
+ *   m  = the smallest dist[r][a_i] over D, L = the entries of D at m.
+ * Outputs, rows in ospf_sweep_roots order, A = offsets[n_prefixes]:
+ *   metric [n][P]   m; OSPF_DIST_INF when R or D is empty;
+ *   count  [n][P]   |L|; a root in L (flag unset) gets metric 0, count 1 and
+ *                   nothing else, as in the policy call;
+ *   need, best [n][P]  as ospf_sweep_select_policy;
+ *   dst_nh [n][A][nh_words]  per ENTRY: the next-hop words of a_i's row when
+ *                   i is in L and a_i != r, else zero; a root's words
+ *                   W .. nh_words are zero;
+ *   dst_links [n][A]  the sum of c(r, k) over the set bits k of dst_nh[i]
+ *                   (c as `links` of ospf_sweep_select_policy);
+ *   links  [n][P]   the sum of dst_links over the prefix's entries: the number
+ *                   of (link, destination) pairs. It equals nextHops.size()
+ *                   of the reference route when every destination's node
+ *                   label is valid, the labels are pairwise distinct and any
+ *                   prepend label is valid -- the engine never sees labels;
+ *                   the consumer builds the PUSH stacks (:1231-1261) and
+ *                   pushes nothing when the next hop IS the destination.
+ *                   The route is installed iff links > 0 and need <= links.
+ * "Do not reach one destination through another" (:1205-1211) cannot fire
+ * here: a next hop k of a destination at distance m has dist[r][k] < m
+ * (metrics >= 1), m is the minimum over D and S' \ D is r itself, so k is not
+ * in S'; it is not evaluated.
+ * Contract, preconditions and errors are ospf_sweep_select_policy's: any
+ * output may be NULL, every word of a wanted output is written exactly once by
+ * plain stores, nothing is written on error.
+ * Not covered: this selection kept resident (ospf_selstate_*) and its delta,
+ * several areas, ospf_msweep, K_SHORTEST_DISTANCE_2, label validity and static
+ * MPLS next hops (:1019-1029). */
+#define OSPF_SEL_SELF_PREPEND 0x1u
+typedef struct ospf_select_stable { /* host memory; ospf_select_ptable + flags */
+  uint32_t n_prefixes;
+  const uint32_t* offsets;     /* [n_prefixes + 1] */
+  const uint32_t* nodes;       /* strictly ascending per prefix */
+  const uint32_t* pref;        /* [offsets[P]], < 2^31, smaller wins */
+  const uint32_t* min_nexthop; /* [offsets[P]] or NULL (all unset) */
+  const uint32_t* flags;       /* [offsets[P]] or NULL (all 0) */
+} ospf_select_stable;
+typedef struct ospf_select_sout {
+  uint32_t *metric, *count, *links, *need, *best; /* [n][P] */
+  uint32_t* dst_links;                            /* [n][A], A = offsets[P] */
+  uint32_t* dst_nh;                               /* [n][A][nh_words] */
+} ospf_select_sout;
+/* device outputs, queued on `stream` after the table's upload */
+int ospf_sweep_select_srmpls_dev(ospf_sweep* sw, const ospf_select_stable* table,
+                                 uint32_t nh_words, const ospf_select_sout* d_out, void* stream);
+/* host outputs, synchronous (after the work queued on every stream) */
+int ospf_sweep_select_srmpls(ospf_sweep* sw, const ospf_select_stable* table, uint32_t nh_words,
+                             const ospf_select_sout* out);
 /* The same selection across several areas (createRouteForPrefix is multi-area
  * at its core, SpfSolver.cpp:229-244, :365-443), for every node of the union
  * of the areas and every prefix, in one launch. Areas 0 .. n_areas - 1 are
@@ -783,8 +846,9 @@ int ospf_sweep_select_policy(ospf_sweep* sw, const ospf_select_ptable* table, ui
  * ascending in (node, area), area >= n_areas, pref >= 2^31 or NULL with
  * entries, an nh_words[a] too small. n_prefixes == 0: OSPF_OK, nothing written.
  * The same selection kept resident and its delta: ospf_areastate_* below.
- * Not covered: UCMP across areas, SR_MPLS per-destination next hops and KSP2,
- * BGP metric vectors, ospf_msweep and several devices. */
+ * Not covered: UCMP across areas, SR_MPLS per-destination next hops across
+ * areas (one area: ospf_sweep_select_srmpls) and KSP2, BGP metric vectors,
+ * ospf_msweep and several devices. */
 typedef struct ospf_areas_table { /* host memory */
   uint32_t n_areas;               /* 1 .. 32 */
   ospf_sweep* const* sweeps;      /* [n_areas] */

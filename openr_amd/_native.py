@@ -43,6 +43,7 @@ ENGINE_SYMBOLS = [
     "ospf_sweep_select_dev", "ospf_sweep_select", "ospf_msweep_select",
     "ospf_sweep_select_policy_dev", "ospf_sweep_select_policy", "ospf_msweep_select_policy",
     "ospf_areas_select_policy_dev", "ospf_areas_select_policy",
+    "ospf_sweep_select_srmpls_dev", "ospf_sweep_select_srmpls",
     "ospf_selstate_create", "ospf_selstate_destroy", "ospf_selstate_last_error",
     "ospf_selstate_device_bytes", "ospf_selstate_prime", "ospf_selstate_update", "ospf_selstate_copy",
     "ospf_selstate_ucmp", "ospf_selstate_ucmp_copy", "ospf_selstate_ucmp_info",
@@ -65,7 +66,7 @@ DECISION_SYMBOLS = [
     "odl_apply_kvs", "odl_apply_publication", "odl_node_patches", "odl_shard_stats", "odl_route_db_multi_text", "odl_adjdbs_decode", "odl_adjdbs_stream", "odl_adjdbs_error", "odl_adjdbs_free",
     "odl_last_decode_error", "odl_get_counters", "odl_last_engine_error", "odl_inject_engine_error",
     "odl_set_degrade", "odl_all_sources_select", "odl_all_sources_select_policy",
-    "odl_areas_select_policy",
+    "odl_areas_select_policy", "odl_all_sources_select_srmpls",
     "odl_areas_track", "odl_areas_untrack", "odl_areas_set_attrs", "odl_areas_delta",
     "odl_areas_tracked",
     "odl_track_select", "odl_select_delta", "odl_select_tracked",
@@ -154,6 +155,16 @@ class ospf_select_ptable(C.Structure):  # noqa: N801
 class ospf_select_pout(C.Structure):  # noqa: N801
     _fields_ = [("metric", vp), ("count", vp), ("nh", vp), ("links", vp), ("need", vp),
                 ("best", vp)]
+
+
+class ospf_select_stable(C.Structure):  # noqa: N801
+    _fields_ = [("n_prefixes", u32), ("offsets", vp), ("nodes", vp), ("pref", vp),
+                ("min_nexthop", vp), ("flags", vp)]
+
+
+class ospf_select_sout(C.Structure):  # noqa: N801
+    _fields_ = [("metric", vp), ("count", vp), ("links", vp), ("need", vp), ("best", vp),
+                ("dst_links", vp), ("dst_nh", vp)]
 
 
 class ospf_areas_table(C.Structure):  # noqa: N801
@@ -257,6 +268,10 @@ def engine() -> C.CDLL:
                                                C.POINTER(ospf_select_pout)]
         L.ospf_msweep_select_policy.argtypes = [vp, C.POINTER(ospf_select_ptable), u32,
                                                 C.POINTER(ospf_select_pout)]
+        L.ospf_sweep_select_srmpls_dev.argtypes = [vp, C.POINTER(ospf_select_stable), u32,
+                                                   C.POINTER(ospf_select_sout), vp]
+        L.ospf_sweep_select_srmpls.argtypes = [vp, C.POINTER(ospf_select_stable), u32,
+                                               C.POINTER(ospf_select_sout)]
         L.ospf_areas_select_policy_dev.argtypes = [C.POINTER(ospf_areas_table),
                                                    C.POINTER(ospf_areas_pout), vp]
         L.ospf_areas_select_policy.argtypes = [C.POINTER(ospf_areas_table),
@@ -328,6 +343,8 @@ def decision() -> C.CDLL:
         L.odl_all_sources_select.argtypes = [vp, cp, u32, i32, u32, C.POINTER(u32), vp, vp, vp]
         L.odl_all_sources_select_policy.argtypes = [vp, cp, u32, vp, u32, i32, u32,
                                                     C.POINTER(u32), vp, vp, vp, vp, vp, vp, vp]
+        L.odl_all_sources_select_srmpls.argtypes = [vp, cp, u32, vp, u32, i32, u32,
+                                                    C.POINTER(u32)] + [vp] * 9
         L.odl_track_select.argtypes = [vp, cp, u32, i32]
         L.odl_select_delta.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32),
                                        C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]

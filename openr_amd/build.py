@@ -27,7 +27,7 @@ ENGINE_SRC = [os.path.join(PKG, "csrc", "engine", f)
                         "spf_sweep.hip", "sweep_units.hip", "sweep_plan_derive.hip",
                         "sweep_plan_weighted.hip", "spf_multi.hip", "spf_select.hip", "spf_seldelta.hip",
                         "spf_ucmp.hip", "spf_selpolicy.hip", "spf_seldelta_policy.hip",
-                        "spf_selareas.hip", "spf_seldelta_areas.hip")]
+                        "spf_selareas.hip", "spf_seldelta_areas.hip", "spf_selsrmpls.hip")]
 DECISION_SRC = [os.path.join(PKG, "csrc", "decision", f)
                 for f in ("link_state.cpp", "spf_solver.cpp", "adjdb_thrift.cpp", "decision_capi.cpp")]
 ENGINE_SO = os.path.join(LIB, "libopenr_spf_hip.so")

@@ -572,6 +572,66 @@ int odl_all_sources_select_policy(odl_ls* h, const char* prefixes_nl, uint32_t n
   }, -1);
 }
 
+int odl_all_sources_select_srmpls(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes,
+                                  const int64_t* attrs, uint32_t n_attrs, int use_link_metric,
+                                  uint32_t nh_words, uint32_t* nh_words_needed,
+                                  uint32_t* entry_offsets, uint32_t* metric, uint32_t* count,
+                                  uint32_t* links, uint32_t* need, uint32_t* best,
+                                  uint32_t* dst_links, uint32_t* dst_nh, uint8_t* installed) {
+  return guard(h, [&]() -> int {
+    const uint32_t words = h->ls.selectWords();
+    if (nh_words_needed) *nh_words_needed = words;
+    if (!nh_words) return 0;  // the width only
+    if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
+    if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
+    std::vector<std::vector<std::string>> prefixes;
+    std::vector<std::vector<odl::LinkState::SelectAttr>> at;
+    std::vector<std::vector<uint8_t>> prepend;
+    size_t used = 0;
+    for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
+      std::vector<std::string> names;
+      std::vector<odl::LinkState::SelectAttr> as;
+      std::vector<uint8_t> pp;
+      for (size_t b = 0; b < ln.size();) {  // tab-separated, empty fields skipped
+        size_t e = ln.find('\t', b);
+        if (e == std::string::npos) e = ln.size();
+        if (e > b) {
+          if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than announcer names");
+          const int64_t* a = attrs + 5 * used++;
+          odl::LinkState::SelectAttr sa;
+          sa.pathPreference = a[0];
+          sa.sourcePreference = a[1];
+          sa.distance = a[2];
+          if (a[3] != std::numeric_limits<int64_t>::min()) sa.minNexthop = a[3];
+          if (a[4] != 0 && a[4] != 1) throw std::invalid_argument("the prepend flag is 0 or 1");
+          names.emplace_back(ln, b, e - b);
+          as.push_back(sa);
+          pp.push_back((uint8_t)a[4]);
+        }
+        b = e + 1;
+      }
+      prefixes.push_back(std::move(names));
+      at.push_back(std::move(as));
+      prepend.push_back(std::move(pp));
+    }
+    if (used != n_attrs) throw std::invalid_argument("more attribute sets than announcer names");
+    const auto r = h->ls.allSourcesSelectSrMpls(prefixes, at, prepend, use_link_metric != 0, nh_words);
+    auto put = [](const auto& src, auto* dst) {
+      if (dst) std::copy(src.begin(), src.end(), dst);
+    };
+    put(r.entryOffsets, entry_offsets);
+    put(r.metric, metric);
+    put(r.count, count);
+    put(r.links, links);
+    put(r.need, need);
+    put(r.best, best);
+    put(r.dstLinks, dst_links);
+    put(r.dstNh, dst_nh);
+    put(r.installed, installed);
+    return 0;
+  }, -1);
+}
+
 namespace {
 // lines of tab-separated (node, area) name pairs with four attributes per entry
 std::vector<std::vector<odl::LinkState::AreaEntry>> areaEntries(const char* prefixes_nl,

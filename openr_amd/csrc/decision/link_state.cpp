@@ -1233,13 +1233,15 @@ void LinkState::policyTable(const std::vector<std::vector<std::string>>& prefixe
                             const std::vector<std::vector<SelectAttr>>& attrs, const char* who,
                             std::vector<std::vector<uint32_t>>& ann,
                             std::vector<std::vector<uint32_t>>& pref,
-                            std::vector<std::vector<uint32_t>>& mnh) const {
+                            std::vector<std::vector<uint32_t>>& mnh,
+                            std::vector<std::vector<uint32_t>>* pos) const {
   if (attrs.size() != prefixes.size())
     throw std::invalid_argument(std::string(who) + ": one attribute list per prefix");
   const size_t P = prefixes.size();
   ann.assign(P, {});
   pref.assign(P, {});
   mnh.assign(P, {});
+  if (pos) pos->assign(P, {});
   for (size_t p = 0; p < P; ++p) {
     if (attrs[p].size() != prefixes[p].size())
       throw std::invalid_argument(std::string(who) + ": one attribute set per announcer");
@@ -1260,6 +1262,7 @@ void LinkState::policyTable(const std::vector<std::vector<std::string>>& prefixe
     for (size_t i = 0; i < ent.size(); ++i) {
       ann[p].push_back(ent[i].first);
       mnh[p].push_back(clampedMinNexthop(kept[i]));
+      if (pos) (*pos)[p].push_back((uint32_t)ent[i].second);
     }
   }
 }
@@ -2038,6 +2041,169 @@ LinkState::PolicyResult LinkState::allSourcesPolicyImpl(
     put(li, out.links, P);
     put(ne, out.need, P);
     put(be, out.best, P);
+  }
+  install();
+  return out;
+}
+
+// ---------------------------------------------------------------- select SR_MPLS
+LinkState::SrMplsResult LinkState::allSourcesSelectSrMpls(
+    const std::vector<std::vector<std::string>>& prefixes,
+    const std::vector<std::vector<SelectAttr>>& attrs,
+    const std::vector<std::vector<uint8_t>>& hasPrepend, bool useLinkMetric, uint32_t nhWords) {
+  snapshot();
+  const uint32_t need = selectWords();
+  if (nhWords && nhWords < need)
+    throw std::invalid_argument("allSourcesSelectSrMpls: nhWords " + std::to_string(nhWords) +
+                                " below the widest node's " + std::to_string(need));
+  std::vector<std::vector<uint32_t>> ann, pref, mnh, pos, flags;
+  policyTable(prefixes, attrs, "allSourcesSelectSrMpls", ann, pref, mnh, &pos);
+  if (hasPrepend.size() != prefixes.size())
+    throw std::invalid_argument("allSourcesSelectSrMpls: one prepend list per prefix");
+  flags.resize(ann.size());
+  for (size_t p = 0; p < ann.size(); ++p) {
+    if (hasPrepend[p].size() != prefixes[p].size())
+      throw std::invalid_argument("allSourcesSelectSrMpls: one prepend flag per announcer");
+    for (uint32_t i : pos[p]) flags[p].push_back(hasPrepend[p][i] ? OSPF_SEL_SELF_PREPEND : 0u);
+  }
+  const uint32_t W = nhWords ? nhWords : need;
+  return guarded([&] { return allSourcesSrMplsImpl(ann, pref, mnh, flags, useLinkMetric, W); });
+}
+
+LinkState::SrMplsResult LinkState::allSourcesSrMplsImpl(
+    const std::vector<std::vector<uint32_t>>& ann, const std::vector<std::vector<uint32_t>>& pref,
+    const std::vector<std::vector<uint32_t>>& mnh, const std::vector<std::vector<uint32_t>>& flags,
+    bool useLinkMetric, uint32_t W) {
+  snapshot();
+  const size_t V = csr_->names.size(), P = ann.size();
+  SrMplsResult out;
+  out.prefixes = (uint32_t)P;
+  out.words = W;
+  out.entryOffsets.assign(P + 1, 0);
+  for (size_t p = 0; p < P; ++p) {
+    out.entryNodes.insert(out.entryNodes.end(), ann[p].begin(), ann[p].end());
+    out.entryOffsets[p + 1] = (uint32_t)out.entryNodes.size();
+  }
+  const size_t A = out.entryNodes.size();
+  out.metric.assign(V * P, kInf);
+  out.count.assign(V * P, 0);
+  out.links.assign(V * P, 0);
+  out.need.assign(V * P, 0);
+  out.best.assign(V * P, kInf);
+  out.dstLinks.assign(V * A, 0);
+  out.dstNh.assign(V * A * W, 0);
+  out.installed.assign(V * P, 0);
+  if (!V || !P) return out;
+  auto install = [&] {
+    for (size_t i = 0; i < V * P; ++i)
+      out.installed[i] = out.links[i] > 0 && out.need[i] <= out.links[i];
+  };
+  // msweep has no SR_MPLS selection: a multi-device LinkState takes the host loop
+  if (hostRun(useLinkMetric) || devices_.size() > 1) {
+    // createRouteForPrefix's steps, then selectBestPathsSpf's per-destination
+    // next hops (SpfSolver.cpp:794-806, 1043-1089) over getSpfResult of every node
+    std::vector<uint32_t> nbrs, minw, c;
+    for (uint32_t r = 0; r < V; ++r) {
+      const SpfResult& res = getSpfResult(csr_->names[r], useLinkMetric);
+      nbrs.clear();
+      for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e)
+        if (csr_->col[e] != r && (nbrs.empty() || nbrs.back() != csr_->col[e]))
+          nbrs.push_back(csr_->col[e]);
+      minw.assign(nbrs.size(), kInf);
+      c.assign(nbrs.size(), 0);
+      auto slot = [&](uint32_t id) {
+        return (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), id) - nbrs.begin());
+      };
+      for (int pass = 0; pass < 2; ++pass)
+        for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e) {
+          if (csr_->col[e] == r || !csr_->edgeUp[e]) continue;
+          const uint32_t k = slot(csr_->col[e]);
+          if (!pass) minw[k] = std::min(minw[k], csr_->metric[e]);
+          else if (!useLinkMetric || csr_->metric[e] == minw[k]) ++c[k];
+        }
+      for (size_t p = 0; p < P; ++p) {
+        const size_t n = ann[p].size();
+        std::vector<size_t> R;
+        std::vector<Metric> d(n, 0);
+        for (size_t i = 0; i < n; ++i) {
+          const auto it = res.find(csr_->names[ann[p][i]]);
+          if (it == res.end()) continue;
+          d[i] = it->second.metric();
+          R.push_back(i);
+        }
+        if (R.empty()) continue;
+        uint32_t top = kInf;
+        for (size_t i : R) top = std::min(top, pref[p][i]);
+        std::vector<size_t> S, Sf, D;
+        for (size_t i : R)
+          if (pref[p][i] == top) S.push_back(i);
+        for (size_t i : S)
+          if (!csr_->noTransit[ann[p][i]]) Sf.push_back(i);
+        if (Sf.empty()) Sf = S;
+        const size_t cell = r * P + p;
+        for (size_t i : Sf) {
+          out.need[cell] = std::max(out.need[cell], mnh[p][i]);
+          // filteredBestNodeAreas: the node's own entry with a prepend label leaves
+          if (!(ann[p][i] == r && (flags[p][i] & OSPF_SEL_SELF_PREPEND))) D.push_back(i);
+        }
+        out.best[cell] = ann[p][S.front()];  // ascending ids: the smallest of S
+        for (size_t i : S)
+          if (ann[p][i] == r) out.best[cell] = r;
+        if (D.empty()) continue;
+        Metric shortest = std::numeric_limits<Metric>::max();
+        for (size_t i : D) shortest = std::min(shortest, d[i]);
+        out.metric[cell] = (uint32_t)shortest;
+        for (size_t i : D) {
+          if (d[i] != shortest) continue;
+          ++out.count[cell];
+          const size_t ent = r * A + out.entryOffsets[p] + i;
+          uint32_t* words = out.dstNh.data() + ent * W;
+          for (const auto& nhName : res.at(csr_->names[ann[p][i]]).nextHops()) {
+            const uint32_t id = csr_->ids.at(nhName);
+            const uint32_t k = slot(id);
+            if (k < nbrs.size() && nbrs[k] == id && k / 32 < W && !(words[k / 32] >> (k % 32) & 1u)) {
+              words[k / 32] |= 1u << (k % 32);
+              out.dstLinks[ent] += c[k];
+            }
+          }
+          out.links[cell] += out.dstLinks[ent];
+        }
+      }
+    }
+    install();
+    return out;
+  }
+  prefetchAllSources(useLinkMetric);
+  std::vector<uint32_t> prefs, mins, fl;
+  for (size_t p = 0; p < P; ++p) {
+    prefs.insert(prefs.end(), pref[p].begin(), pref[p].end());
+    mins.insert(mins.end(), mnh[p].begin(), mnh[p].end());
+    fl.insert(fl.end(), flags[p].begin(), flags[p].end());
+  }
+  const ospf_select_stable t{(uint32_t)P,  out.entryOffsets.data(), out.entryNodes.data(),
+                             prefs.data(), mins.data(),             fl.data()};
+  ospf_sweep_info info{};
+  ospf_sweep_get_info(sweep_, &info);
+  std::vector<uint32_t> roots(info.n_roots);
+  ospf_sweep_roots(sweep_, roots.data());
+  const size_t n = roots.size();
+  std::vector<uint32_t> m(n * P), k(n * P), li(n * P), ne(n * P), be(n * P), dl(n * A),
+      dn(n * A * W);
+  const ospf_select_sout o{m.data(), k.data(), li.data(), ne.data(), be.data(), dl.data(), dn.data()};
+  const int rc = ospf_sweep_select_srmpls(sweep_, &t, W, &o);
+  if (rc != OSPF_OK) throw EngineError(rc, ospf_sweep_last_error(sweep_));
+  for (size_t i = 0; i < n; ++i) {  // owned-roots order -> node id
+    const size_t r = roots[i];
+    auto put = [&](const std::vector<uint32_t>& src, std::vector<uint32_t>& dst, size_t per) {
+      std::copy(src.begin() + i * per, src.begin() + (i + 1) * per, dst.begin() + r * per);
+    };
+    put(m, out.metric, P);
+    put(k, out.count, P);
+    put(li, out.links, P);
+    put(ne, out.need, P);
+    put(be, out.best, P);
+    put(dl, out.dstLinks, A);
+    put(dn, out.dstNh, A * W);
   }
   install();
   return out;

@@ -570,8 +570,9 @@ class LinkState {
   // installed = 1 iff links > 0 and need <= links. For a name given twice the
   // first occurrence counts; unknown names are dropped with their attributes.
   // On the host path the same rule runs over getSpfResult of every node.
-  // Not covered: SR_MPLS per-destination next hops, KSP2 / per-area distance
-  // selection, BGP metric vectors. Several areas: allAreasSelect.
+  // SR_MPLS per-destination next hops: allSourcesSelectSrMpls below. Not
+  // covered: KSP2 / per-area distance selection, BGP metric vectors. Several
+  // areas: allAreasSelect.
   struct SelectAttr {
     int64_t pathPreference = 0, sourcePreference = 0, distance = 0;
     std::optional<int64_t> minNexthop;
@@ -585,6 +586,33 @@ class LinkState {
   PolicyResult allSourcesSelect(const std::vector<std::vector<std::string>>& prefixes,
                                 const std::vector<std::vector<SelectAttr>>& attrs,
                                 bool useLinkMetric = true, uint32_t nhWords = 0);
+  // The same selection for prefixes forwarded as SR_MPLS (selectBestPathsSpf
+  // with perDestination, SpfSolver.cpp:772-845; ospf_sweep_select_srmpls):
+  // the next hops are kept per destination -- per kept entry of the table --
+  // instead of ORed, and a node whose own entry has a prepend label
+  // (hasPrepend, parallel to `attrs`) routes to the other announcers
+  // (:794-802). entryOffsets [prefixes + 1] / entryNodes index the kept
+  // entries (policyTable's: unknown names dropped, the first occurrence of a
+  // name, ascending by id), A of them; dstLinks is [V][A], dstNh [V][A][words];
+  // links = the (link, destination) pairs of the route, which is
+  // nextHops.size() when the node labels are valid and distinct and a prepend
+  // label valid (labels are the consumer's: it builds the PUSH stacks). On one
+  // device the engine answers; in host mode, on a multi-device LinkState and
+  // after a device error the same rule runs over getSpfResult of every node.
+  // Not covered: the selection kept resident and its delta, several areas,
+  // KSP2, static MPLS next hops.
+  struct SrMplsResult {
+    uint32_t prefixes = 0, words = 0;
+    std::vector<uint32_t> entryOffsets, entryNodes;           // [prefixes + 1], [A]
+    std::vector<uint32_t> metric, count, links, need, best;  // [V][prefixes]
+    std::vector<uint32_t> dstLinks;                           // [V][A]
+    std::vector<uint32_t> dstNh;                              // [V][A][words]
+    std::vector<uint8_t> installed;                           // [V][prefixes]
+  };
+  SrMplsResult allSourcesSelectSrMpls(const std::vector<std::vector<std::string>>& prefixes,
+                                      const std::vector<std::vector<SelectAttr>>& attrs,
+                                      const std::vector<std::vector<uint8_t>>& hasPrepend,
+                                      bool useLinkMetric = true, uint32_t nhWords = 0);
   // next-hop words of the widest node of the snapshot
   uint32_t selectWords();
   // The same selection across several areas, one LinkState each
@@ -609,8 +637,9 @@ class LinkState {
   // none and the error is thrown); any other engine refusal (contract, LDS
   // size) sends only this call to the host.
   // The same selection kept resident and its delta: AreasTracker below.
-  // Not covered: UCMP across areas, SR_MPLS per-destination next hops and
-  // KSP2, BGP metric vectors, several devices.
+  // Not covered: UCMP across areas, SR_MPLS per-destination next hops across
+  // areas (one area: allSourcesSelectSrMpls) and KSP2, BGP metric vectors,
+  // several devices.
   struct AreaEntry {
     std::string node, area;
     SelectAttr attr;
@@ -1026,12 +1055,19 @@ class LinkState {
                                     const std::vector<std::vector<uint32_t>>& pref,
                                     const std::vector<std::vector<uint32_t>>& mnh,
                                     bool useLinkMetric, uint32_t W);
+  SrMplsResult allSourcesSrMplsImpl(const std::vector<std::vector<uint32_t>>& ann,
+                                    const std::vector<std::vector<uint32_t>>& pref,
+                                    const std::vector<std::vector<uint32_t>>& mnh,
+                                    const std::vector<std::vector<uint32_t>>& flags,
+                                    bool useLinkMetric, uint32_t W);
   // names -> ids (unknown names dropped with their attributes, the first
-  // occurrence counts, ascending), class ranks and clamped thresholds
+  // occurrence counts, ascending), class ranks and clamped thresholds; `pos`
+  // (may be null): each kept entry's position in its prefix's given list
   void policyTable(const std::vector<std::vector<std::string>>& prefixes,
                    const std::vector<std::vector<SelectAttr>>& attrs, const char* who,
                    std::vector<std::vector<uint32_t>>& ann, std::vector<std::vector<uint32_t>>& pref,
-                   std::vector<std::vector<uint32_t>>& mnh) const;
+                   std::vector<std::vector<uint32_t>>& mnh,
+                   std::vector<std::vector<uint32_t>>* pos = nullptr) const;
   // the dense class rank of each attribute set among the given ones, and the
   // clamped threshold (policyTable's, shared with allAreasSelect)
   static std::vector<uint32_t> classRanks(const std::vector<SelectAttr>& attrs);

@@ -35,8 +35,8 @@
 // resident state and its delta (spf_seldelta_areas.hip).
 //
 // Out of scope (include/openr_spf.h says so too): UCMP across areas, SR_MPLS
-// per-destination next hops and KSP2, BGP metric vectors, ospf_msweep and
-// several devices.
+// per-destination next hops across areas (one area: spf_selsrmpls.hip) and
+// KSP2, BGP metric vectors, ospf_msweep and several devices.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

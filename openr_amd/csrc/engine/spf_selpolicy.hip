@@ -21,9 +21,10 @@
 // its set next-hop bits. Every word of a wanted output is written once by
 // plain vector stores; no memset, no global atomics, no scratch.
 //
-// Out of scope (include/openr_spf.h says so too): SR_MPLS per-destination
-// next hops, K_SHORTEST_DISTANCE_2 and PER_AREA_SHORTEST_DISTANCE, BGP metric
-// vectors. (Several areas: spf_selareas.hip. A policy table in ospf_selstate_*:
+// Out of scope (include/openr_spf.h says so too): K_SHORTEST_DISTANCE_2 and
+// PER_AREA_SHORTEST_DISTANCE, BGP metric vectors. (SR_MPLS per-destination next
+// hops: spf_selsrmpls.hip, one area and one sweep. Several areas:
+// spf_selareas.hip. A policy table in ospf_selstate_*:
 // spf_seldelta_policy.hip.)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -132,17 +133,17 @@ __global__ __launch_bounds__(256) void policy_kernel(const PolicyArgs a) {
 
 using namespace ospf_int::sweep;
 
-uint32_t max_row_words(const ospf_sweep* s) {
-  uint32_t mw = 0;
-  for (uint32_t r : s->roots) mw = std::max(mw, s->row_w[r]);
-  return mw;
-}
-
 bool any_out(const ospf_select_pout* o) {
   return o->metric || o->count || o->nh || o->links || o->need || o->best;
 }
 
 }  // namespace
+
+uint32_t ospf_int::sweep::policy_row_words(const ospf_sweep* s) {
+  uint32_t mw = 0;
+  for (uint32_t r : s->roots) mw = std::max(mw, s->row_w[r]);
+  return mw;
+}
 
 // the policy table's contract beyond ospf_select_table's
 const char* ospf_int::sweep::select_ptable_check(const ospf_select_ptable* t, uint32_t V) {
@@ -156,20 +157,11 @@ const char* ospf_int::sweep::select_ptable_check(const ospf_select_ptable* t, ui
   return nullptr;
 }
 
-// ospf_sweep_select_policy_dev without the fault-injection hook (the host and
-// multi-device calls hook once themselves)
-int ospf_int::sweep::policy_queue(ospf_sweep* s, const ospf_select_ptable* t, uint32_t nh_words,
-                                  const ospf_select_pout* d_out, void* stream) {
+// the device side of a policy table (sweep_impl.h)
+int ospf_int::sweep::policy_upload(ospf_sweep* s, const ospf_select_ptable* t,
+                                   const uint32_t* flags, PolicyTab* d) {
   ospf_ctx* c = s->c;
-  if (!s->ran) return sfail(s, OSPF_E_INVAL, "sweep: select before the first run");
-  if (const char* bad = select_ptable_check(t, s->V)) return sfail(s, OSPF_E_INVAL, bad);
-  if (nh_words < max_row_words(s))
-    return sfail(s, OSPF_E_INVAL, "sweep: nh_words below a root's next-hop words");
-  // the kernel reads the live CSR and no-transit bits beside the rows
-  if (!c || !c->loaded || c->graph_gen != s->gen || c->mask.on || c->info.n_nodes != s->V)
-    return sfail(s, OSPF_E_INVAL, "select policy: the graph changed since the sweep was created");
-  const uint32_t n = (uint32_t)s->roots.size(), P = t->n_prefixes;
-  if (!n || !P || !any_out(d_out)) return OSPF_OK;
+  const uint32_t P = t->n_prefixes;
   SCHK(s, hipSetDevice(c->device));
   if (const int rc = select_rows(s)) return rc;
   if (!s->d_pol_roots) {
@@ -179,7 +171,7 @@ int ospf_int::sweep::policy_queue(ospf_sweep* s, const ospf_select_ptable* t, ui
   }
   // the table's device copy (offsets, nodes, pref, min_nexthop): the buffer is
   // the last call's, free once that call's kernel is done
-  const size_t A = t->offsets[P], words = (size_t)P + 1 + 3 * A;
+  const size_t A = t->offsets[P], words = (size_t)P + 1 + (flags ? 4 : 3) * A;
   if (s->pol_ev) SCHK(s, hipEventSynchronize(s->pol_ev));
   if (words > s->pol_tab_words) {
     if (s->d_pol_tab) SCHK(s, hipFree(s->d_pol_tab));
@@ -205,6 +197,28 @@ int ospf_int::sweep::policy_queue(ospf_sweep* s, const ospf_select_ptable* t, ui
       SCHK(s, hipMemcpy(d_mnh, t->min_nexthop, A * 4, hipMemcpyHostToDevice));
   }
   if (!s->pol_ev) SCHK(s, hipEventCreateWithFlags(&s->pol_ev, hipEventDisableTiming));
+  if (flags && A) SCHK(s, hipMemcpy(d_mnh + A, flags, A * 4, hipMemcpyHostToDevice));
+  *d = PolicyTab{d_off, d_nodes, d_pref, t->min_nexthop && A ? d_mnh : nullptr,
+                 flags && A ? d_mnh + A : nullptr};
+  return OSPF_OK;
+}
+
+// ospf_sweep_select_policy_dev without the fault-injection hook (the host and
+// multi-device calls hook once themselves)
+int ospf_int::sweep::policy_queue(ospf_sweep* s, const ospf_select_ptable* t, uint32_t nh_words,
+                                  const ospf_select_pout* d_out, void* stream) {
+  ospf_ctx* c = s->c;
+  if (!s->ran) return sfail(s, OSPF_E_INVAL, "sweep: select before the first run");
+  if (const char* bad = select_ptable_check(t, s->V)) return sfail(s, OSPF_E_INVAL, bad);
+  if (nh_words < policy_row_words(s))
+    return sfail(s, OSPF_E_INVAL, "sweep: nh_words below a root's next-hop words");
+  // the kernel reads the live CSR and no-transit bits beside the rows
+  if (!c || !c->loaded || c->graph_gen != s->gen || c->mask.on || c->info.n_nodes != s->V)
+    return sfail(s, OSPF_E_INVAL, "select policy: the graph changed since the sweep was created");
+  const uint32_t n = (uint32_t)s->roots.size(), P = t->n_prefixes;
+  if (!n || !P || !any_out(d_out)) return OSPF_OK;
+  PolicyTab d{};
+  if (const int rc = policy_upload(s, t, nullptr, &d)) return rc;
   PolicyArgs a{};
   a.rows = s->d_sel_rows;
   a.roots = s->d_pol_roots;
@@ -213,7 +227,7 @@ int ospf_int::sweep::policy_queue(ospf_sweep* s, const ospf_select_ptable* t, ui
   a.Wout = nh_words;
   a.hop = (s->opts.flags & OSPF_HOP_COUNT) ? 1u : 0u;
   a.cap = std::max(1u, c->max_dn);
-  a.t = Table{d_off, d_nodes, d_pref, t->min_nexthop && A ? d_mnh : nullptr, c->g.nt_bits};
+  a.t = Table{d.off, d.nodes, d.pref, d.mnh, c->g.nt_bits};
   a.row_ptr = c->g.row_ptr;
   a.colx = c->g.colx;
   a.w = c->g.w;

@@ -1,7 +1,8 @@
 // spf_selpolicy_dev.h — the per-prefix device functions of route selection
 // under the reference's best-route policy (spf_selpolicy.hip: policy_kernel,
 // the one-shot selection; spf_seldelta_policy.hip: seldelta_policy_kernel,
-// the resident selection and its delta). Per (root r, prefix p) createRouteForPrefix
+// the resident selection and its delta; spf_selsrmpls.hip: srmpls_kernel, the
+// same selection with per-destination next hops). Per (root r, prefix p) createRouteForPrefix
 // (openr/decision/SpfSolver.cpp:197-458) before it takes the minimum
 //   R  = the announcers r reaches                                  (:229-244)
 //   S  = those of R in the best (path pref, source pref, distance) class
@@ -160,6 +161,19 @@ __device__ __forceinline__ void policy_reduce(uint32_t need, uint32_t smallest, 
   e.best = best_of(wave_min(smallest), __ballot(has_root) != 0ull, r);
 }
 
+// one reached entry's share of need / best under the smallest key kmin: its
+// id into the class's smallest id and root flag when it is of S, its
+// threshold into need when it is of S'
+__device__ __forceinline__ void class_fold(const Table& t, uint64_t key, uint64_t kmin, uint32_t k,
+                                           uint32_t id, uint32_t r, uint32_t& need,
+                                           uint32_t& smallest, bool& has_root) {
+  if (key != kNoKey && (key >> 33) == (kmin >> 33)) {
+    smallest = min(smallest, id);
+    has_root = has_root || id == r;
+  }
+  if (key != kNoKey && (key >> 32) == (kmin >> 32) && t.mnh) need = max(need, t.mnh[k]);
+}
+
 // A long prefix by the whole wave, a lane per announcer (W <= kSelLaneW):
 // wave-uniform entry and words. Pass 2 re-reads the ids and folds count,
 // words, need and best into the one walk.
@@ -181,11 +195,7 @@ __device__ __forceinline__ void policy_by_lanes(const Table& t, const uint32_t* 
     uint64_t key = kNoKey;
     if (k < hi) key = key_at(t, dist, k, id);
     const bool tight = key == kmin;
-    if (key != kNoKey && (key >> 33) == (kmin >> 33)) {
-      smallest = min(smallest, id);
-      has_root = has_root || id == r;
-    }
-    if (key != kNoKey && (key >> 32) == (kmin >> 32) && t.mnh) need = max(need, t.mnh[k]);
+    class_fold(t, key, kmin, k, id, r, need, smallest, has_root);
     cnt += (uint32_t)__popcll(__ballot(tight));
     if (tight && want_nh) {
       const uint32_t* row = nh + (size_t)id * W;
@@ -235,11 +245,7 @@ __device__ __forceinline__ uint32_t policy_by_words(const Table& t,
         unsigned long long mask = __ballot(key == kmin);
         if (wb == 0) {
           cnt += (uint32_t)__popcll(mask);
-          if (key != kNoKey && (key >> 33) == (kmin >> 33)) {
-            smallest = min(smallest, id);
-            has_root = has_root || id == r;
-          }
-          if (key != kNoKey && (key >> 32) == (kmin >> 32) && t.mnh) need = max(need, t.mnh[k]);
+          class_fold(t, key, kmin, k, id, r, need, smallest, has_root);
         }
         while (mask) {  // wave-uniform
           const uint32_t j = (uint32_t)__ffsll((long long)mask) - 1u;

@@ -292,6 +292,21 @@ int policy_queue(ospf_sweep* s, const ospf_select_ptable* t, uint32_t nh_words,
 // the policy table's contract (ospf_select_ptable) for a graph of V nodes:
 // null when it holds, else what is wrong
 const char* select_ptable_check(const ospf_select_ptable* t, uint32_t V);
+// the widest next-hop row among the owned roots, in words
+uint32_t policy_row_words(const ospf_sweep* s);
+// What a policy launch reads beside the rows, made ready on the device: the
+// rows table (select_rows), the owned roots' ids (s->d_pol_roots) and the
+// table's columns copied into s->d_pol_tab (offsets, nodes, pref, min_nexthop,
+// then `flags` when given: one word per entry, ospf_select_stable's), after a
+// host wait for the last launch that read that buffer. The caller records
+// s->pol_ev behind its kernel.
+struct PolicyTab {
+  const uint32_t *off, *nodes, *pref, *mnh, *flags;  // device; mnh / flags null when not given
+};
+int policy_upload(ospf_sweep* s, const ospf_select_ptable* t, const uint32_t* flags, PolicyTab* d);
+// ospf_sweep_select_srmpls_dev without the fault-injection hook
+int srmpls_queue(ospf_sweep* s, const ospf_select_stable* t, uint32_t nh_words,
+                 const ospf_select_sout* d_out, void* stream);
 
 // device outputs of one policy select (only the wanted ones of `want`), freed
 // by the destructor

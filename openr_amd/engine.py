@@ -73,6 +73,24 @@ def _policy_host_out(n: int, P: int, W: int, want: Sequence[str]):
     return o, arrs
 
 
+SRMPLS_OUTPUTS = ("metric", "count", "links", "need", "best", "dst_links", "dst_nh")
+
+
+def select_stable(offsets: Sequence[int], nodes: Sequence[int], pref: Optional[Sequence[int]],
+                  min_nexthop: Optional[Sequence[int]] = None,
+                  flags: Optional[Sequence[int]] = None):
+    """(ospf_select_stable, the arrays it points into): select_ptable's table
+    with a flag word per announcer entry (bit 0: the entry has a prepend
+    label, OSPF_SEL_SELF_PREPEND); flags None passes NULL (all 0)."""
+    pt, (off, ids, pr, mn) = select_ptable(offsets, nodes, pref, min_nexthop)
+    fl = None if flags is None else np.ascontiguousarray(flags, np.uint32)
+    if fl is not None and fl.size != ids.size:
+        raise ValueError("flags: one per announcer entry")
+    t = N.ospf_select_stable(pt.n_prefixes, pt.offsets, pt.nodes, pt.pref, pt.min_nexthop,
+                             fl.ctypes.data if fl is not None and fl.size else None)
+    return t, (off, ids, pr, mn, fl)
+
+
 AREAS_OUTPUTS = ("metric", "count", "links", "need", "best", "areas", "nh")
 
 
@@ -576,6 +594,44 @@ class Sweep:
         o = N.ospf_select_pout(d_metric or None, d_count or None, d_nh or None, d_links or None,
                                d_need or None, d_best or None)
         self._check(self._L.ospf_sweep_select_policy_dev(self._h, C.byref(t), nh_words,
+                                                         C.byref(o), stream or None))
+
+    def select_srmpls(self, offsets: Sequence[int], nodes: Sequence[int],
+                      pref: Optional[Sequence[int]],
+                      min_nexthop: Optional[Sequence[int]] = None,
+                      flags: Optional[Sequence[int]] = None, nh_words: int = 0,
+                      want: Sequence[str] = SRMPLS_OUTPUTS) -> Dict[str, np.ndarray]:
+        """ospf_sweep_select_srmpls: select_policy's selection for prefixes
+        forwarded as SR_MPLS, the next hops kept per destination (table entry)
+        -> {metric, count, links, need, best [n, P] u32, dst_links [n, A] u32,
+        dst_nh [n, A, W] u32} in `roots` order, A = offsets[-1]; flags: bit 0
+        per entry = it has a prepend label (an announcing root with it routes
+        to the other announcers). Only the outputs named in `want` are
+        computed; dst_nh is the large one."""
+        bad = set(want) - set(SRMPLS_OUTPUTS)
+        if bad:
+            raise ValueError(f"unknown outputs {sorted(bad)}")
+        t, keep = select_stable(offsets, nodes, pref, min_nexthop, flags)
+        W = nh_words or max(1, self.max_nh_words)
+        n, P, A = self.n_roots, int(t.n_prefixes), int(keep[1].size)
+        shape = {"dst_links": (n, A), "dst_nh": (n, A, W)}
+        arrs = {k: np.zeros(shape.get(k, (n, P)), np.uint32) for k in want}
+        o = N.ospf_select_sout(*[arrs[k].ctypes.data if k in arrs else None
+                                 for k in SRMPLS_OUTPUTS])
+        self._check(self._L.ospf_sweep_select_srmpls(self._h, C.byref(t), W, C.byref(o)))
+        return arrs
+
+    def select_srmpls_dev(self, offsets: Sequence[int], nodes: Sequence[int],
+                          pref: Optional[Sequence[int]], min_nexthop: Optional[Sequence[int]],
+                          flags: Optional[Sequence[int]], nh_words: int, *, d_metric: int = 0,
+                          d_count: int = 0, d_links: int = 0, d_need: int = 0, d_best: int = 0,
+                          d_dst_links: int = 0, d_dst_nh: int = 0, stream: int = 0) -> None:
+        """ospf_sweep_select_srmpls_dev: the same into device memory (raw
+        pointers; 0 = not wanted), queued on `stream` after the table's upload."""
+        t, keep = select_stable(offsets, nodes, pref, min_nexthop, flags)
+        o = N.ospf_select_sout(d_metric or None, d_count or None, d_links or None, d_need or None,
+                               d_best or None, d_dst_links or None, d_dst_nh or None)
+        self._check(self._L.ospf_sweep_select_srmpls_dev(self._h, C.byref(t), nh_words,
                                                          C.byref(o), stream or None))
 
     def profile(self, reps: int = 3):

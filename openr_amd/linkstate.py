@@ -784,6 +784,47 @@ class LinkState:
         out["installed"] = inst.astype(bool)
         return out
 
+    def all_sources_select_srmpls(self, prefixes: Dict[str, Sequence[tuple]],
+                                  use_link_metric: bool = True, nh_words: int = 0) -> dict:
+        """all_sources_select_policy for prefixes forwarded as SR_MPLS
+        (odl_all_sources_select_srmpls; selectBestPathsSpf with perDestination,
+        SpfSolver.cpp:772-845): the next hops are kept per destination.
+        prefixes: {prefix: [(name, path_pref, source_pref, distance,
+        min_nexthop_or_None, has_prepend), ...]}; a node whose own entry has a
+        prepend label routes to the other announcers. Returns a dict by node id:
+        metric / count / links / need / best [V, P] u32, installed [V, P] bool,
+        entry_offsets [P + 1] (the kept entries of each prefix: unknown names
+        dropped, ascending by node id; A = entry_offsets[-1]), dst_links [V, A]
+        u32 and dst_nh [V, A, W] u32 per kept entry. links counts (link,
+        destination) pairs."""
+        lines, at4 = self._policy_lines({k: [a[:5] for a in v] for k, v in prefixes.items()})
+        flag = np.array([int(bool(a[5])) for v in prefixes.values() for a in v], np.int64)
+        at = np.ascontiguousarray(np.concatenate([at4, flag.reshape(-1, 1)], axis=1), np.int64)
+        txt = "\n".join(lines).encode()
+        args = (self._h, txt, len(lines), at.ctypes.data if at.size else None, at.shape[0],
+                int(use_link_metric))
+        need = C.c_uint32(0)
+        if self._L.odl_all_sources_select_srmpls(*args, 0, C.byref(need), *[None] * 9) != 0:
+            raise LinkStateError(self._err())
+        V, P, W = self.num_nodes(), len(lines), nh_words or int(need.value)
+        cap = at.shape[0]  # the kept entries are at most the names given
+        out = {k: np.zeros((V, P), np.uint32) for k in ("metric", "count", "links", "need", "best")}
+        off = np.zeros(P + 1, np.uint32)
+        dl = np.zeros(V * cap, np.uint32)
+        dn = np.zeros(V * cap * W, np.uint32)
+        inst = np.zeros((V, P), np.uint8)
+        if self._L.odl_all_sources_select_srmpls(
+                *args, W, None, off.ctypes.data, out["metric"].ctypes.data,
+                out["count"].ctypes.data, out["links"].ctypes.data, out["need"].ctypes.data,
+                out["best"].ctypes.data, dl.ctypes.data, dn.ctypes.data, inst.ctypes.data) != 0:
+            raise LinkStateError(self._err())
+        A = int(off[-1])
+        out["entry_offsets"] = off
+        out["dst_links"] = dl[:V * A].reshape(V, A)
+        out["dst_nh"] = dn[:V * A * W].reshape(V, A, W)
+        out["installed"] = inst.astype(bool)
+        return out
+
     @staticmethod
     def _policy_lines(prefixes: Dict[str, Sequence[tuple]]):
         """{prefix: [(name, path_pref, source_pref, distance, min_nexthop_or_None)]}

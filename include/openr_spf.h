@@ -569,7 +569,13 @@ typedef struct ospf_sweep_opts {
   uint32_t part;       /* this part of the root partition ... */
   uint32_t n_parts;    /* ... over n_parts (0 or 1: every node) */
   uint32_t hip_graph;  /* 1: capture one run as a HIP graph, runs replay it
-                          (eager launches if capture fails: see info) */
+                          (eager launches if capture fails: see info).
+                          Open: with 32 contexts alive in one process, each
+                          with a graph sweep, the replay of a graph with
+                          several width classes has ended the process with a
+                          segmentation fault once; the cause is not found
+                          (DESIGN.md section 2). A process that keeps tens of
+                          contexts alive should pass 0. */
 } ospf_sweep_opts;
 
 typedef struct ospf_sweep_info {

@@ -47,12 +47,13 @@ def product_tables(areas, table):
 def check_against_route_build(areas, table, exp):
     """every non-announcing node's route of every prefix: igp cost, the
     (neighbour, area) set decoded from nh, best, selected, and whether a route
-    exists against installed"""
+    exists against installed. -> the (global node, prefix) cells whose route was
+    compared"""
     gnames, gids = AR.union(areas)
     routes, _ = product_tables(areas, table)
     dbs = route_dbs_multi([a["ls"] for a in areas], gnames, routes, best_route_selection=True)
     ids = [{n: i for i, n in enumerate(a["names"])} for a in areas]
-    checked = 0
+    checked = []
     for g, me in enumerate(gnames):
         db = dbs[me]
         for p, ents in enumerate(table):
@@ -80,8 +81,9 @@ def check_against_route_build(areas, table, exp):
             assert best == (gnames[e[0]], areas[e[1]]["name"]), (me, p)
             want = {(gnames[ents[i][0]], areas[ents[i][1]]["name"]) for i in exp["selected"][g, p]}
             assert set(sel) == want, (me, p)
-            checked += 1
+            checked.append((g, p))
     assert checked
+    return checked
 
 
 def check_host_call(areas, table, exp, hop=False):

@@ -118,6 +118,49 @@ std::vector<std::vector<std::string>> prefixLines(const char* prefixes_nl, uint3
   return prefixes;
 }
 
+// one attribute set of the C API: path preference, source preference,
+// distance, minNexthop or INT64_MIN for unset
+odl::LinkState::SelectAttr attrOf(const int64_t* a) {
+  odl::LinkState::SelectAttr sa;
+  sa.pathPreference = a[0];
+  sa.sourcePreference = a[1];
+  sa.distance = a[2];
+  if (a[3] != std::numeric_limits<int64_t>::min()) sa.minNexthop = a[3];
+  return sa;
+}
+
+// attribute sets (4 int64 each, attrOf's) -> one list per prefix, parallel to
+// `names`; with `prepend` 5 each: a prepend flag (0 or 1) follows, listed there
+std::vector<std::vector<odl::LinkState::SelectAttr>> attrLists(
+    const std::vector<std::vector<std::string>>& names, const int64_t* attrs, uint32_t n_attrs,
+    std::vector<std::vector<uint8_t>>* prepend = nullptr) {
+  if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
+  std::vector<std::vector<odl::LinkState::SelectAttr>> at;
+  size_t used = 0;
+  for (const auto& ln : names) {
+    std::vector<odl::LinkState::SelectAttr> as;
+    std::vector<uint8_t> pp;
+    for (size_t i = 0; i < ln.size(); ++i) {
+      if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than announcer names");
+      const int64_t* a = attrs + (prepend ? 5 : 4) * used++;
+      as.push_back(attrOf(a));
+      if (!prepend) continue;
+      if (a[4] != 0 && a[4] != 1) throw std::invalid_argument("the prepend flag is 0 or 1");
+      pp.push_back((uint8_t)a[4]);
+    }
+    at.push_back(std::move(as));
+    if (prepend) prepend->push_back(std::move(pp));
+  }
+  if (used != n_attrs) throw std::invalid_argument("more attribute sets than announcer names");
+  return at;
+}
+
+// a result column to the caller's array, when the caller asked for it
+template <class T>
+void copyOut(const std::vector<T>& v, T* dst) {
+  if (dst) std::copy(v.begin(), v.end(), dst);
+}
+
 template <class T>
 void* dupVec(const std::vector<T>& v) {
   void* p = std::malloc(std::max<size_t>(1, v.size() * sizeof(T)));
@@ -411,53 +454,14 @@ int odl_all_sources_select(odl_ls* h, const char* prefixes_nl, uint32_t n_prefix
     const uint32_t need = h->ls.selectWords();
     if (nh_words_needed) *nh_words_needed = need;
     if (!nh_words) return 0;  // the width only
-    if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
-    std::vector<std::vector<std::string>> prefixes;
-    prefixes.reserve(n_prefixes);
-    for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
-      std::vector<std::string> names;
-      for (size_t b = 0; b < ln.size();) {  // tab-separated, empty fields skipped
-        size_t e = ln.find('\t', b);
-        if (e == std::string::npos) e = ln.size();
-        if (e > b) names.emplace_back(ln, b, e - b);
-        b = e + 1;
-      }
-      prefixes.push_back(std::move(names));
-    }
-    const auto r = h->ls.allSourcesSelect(prefixes, use_link_metric != 0, nh_words);
-    if (metric) std::copy(r.metric.begin(), r.metric.end(), metric);
-    if (count) std::copy(r.count.begin(), r.count.end(), count);
-    if (nh) std::copy(r.nh.begin(), r.nh.end(), nh);
+    const auto r = h->ls.allSourcesSelect(prefixLines(prefixes_nl, n_prefixes),
+                                          use_link_metric != 0, nh_words);
+    copyOut(r.metric, metric);
+    copyOut(r.count, count);
+    copyOut(r.nh, nh);
     return 0;
   }, -1);
 }
-
-namespace {
-// attribute sets (4 int64 each: path preference, source preference, distance,
-// minNexthop or INT64_MIN for unset) -> one list per prefix, parallel to `names`
-std::vector<std::vector<odl::LinkState::SelectAttr>> attrLists(
-    const std::vector<std::vector<std::string>>& names, const int64_t* attrs, uint32_t n_attrs) {
-  if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
-  std::vector<std::vector<odl::LinkState::SelectAttr>> at;
-  size_t used = 0;
-  for (const auto& ln : names) {
-    std::vector<odl::LinkState::SelectAttr> as;
-    for (size_t i = 0; i < ln.size(); ++i) {
-      if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than announcer names");
-      const int64_t* a = attrs + 4 * used++;
-      odl::LinkState::SelectAttr sa;
-      sa.pathPreference = a[0];
-      sa.sourcePreference = a[1];
-      sa.distance = a[2];
-      if (a[3] != std::numeric_limits<int64_t>::min()) sa.minNexthop = a[3];
-      as.push_back(sa);
-    }
-    at.push_back(std::move(as));
-  }
-  if (used != n_attrs) throw std::invalid_argument("more attribute sets than announcer names");
-  return at;
-}
-}  // namespace
 
 int odl_track_select_policy(odl_ls* h, const char* prefixes_nl, uint32_t n_prefixes,
                             const int64_t* attrs, uint32_t n_attrs, int use_link_metric) {
@@ -510,13 +514,13 @@ int odl_policy_tracked(odl_ls* h, const char* nodes_nl, uint32_t n, uint32_t nh_
                        uint32_t* need, uint32_t* best, uint8_t* installed) {
   return guard(h, [&]() -> int {
     const auto r = h->ls.policyTracked(splitNl(nodes_nl ? nodes_nl : "", n), nh_words);
-    if (metric) std::copy(r.metric.begin(), r.metric.end(), metric);
-    if (count) std::copy(r.count.begin(), r.count.end(), count);
-    if (nh) std::copy(r.nh.begin(), r.nh.end(), nh);
-    if (links) std::copy(r.links.begin(), r.links.end(), links);
-    if (need) std::copy(r.need.begin(), r.need.end(), need);
-    if (best) std::copy(r.best.begin(), r.best.end(), best);
-    if (installed) std::copy(r.installed.begin(), r.installed.end(), installed);
+    copyOut(r.metric, metric);
+    copyOut(r.count, count);
+    copyOut(r.nh, nh);
+    copyOut(r.links, links);
+    copyOut(r.need, need);
+    copyOut(r.best, best);
+    copyOut(r.installed, installed);
     return 0;
   }, -1);
 }
@@ -530,44 +534,16 @@ int odl_all_sources_select_policy(odl_ls* h, const char* prefixes_nl, uint32_t n
     const uint32_t words = h->ls.selectWords();
     if (nh_words_needed) *nh_words_needed = words;
     if (!nh_words) return 0;  // the width only
-    if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
-    if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
-    std::vector<std::vector<std::string>> prefixes;
-    std::vector<std::vector<odl::LinkState::SelectAttr>> at;
-    prefixes.reserve(n_prefixes);
-    at.reserve(n_prefixes);
-    size_t used = 0;
-    for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
-      std::vector<std::string> names;
-      std::vector<odl::LinkState::SelectAttr> as;
-      for (size_t b = 0; b < ln.size();) {  // tab-separated, empty fields skipped
-        size_t e = ln.find('\t', b);
-        if (e == std::string::npos) e = ln.size();
-        if (e > b) {
-          if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than announcer names");
-          const int64_t* a = attrs + 4 * used++;
-          odl::LinkState::SelectAttr sa;
-          sa.pathPreference = a[0];
-          sa.sourcePreference = a[1];
-          sa.distance = a[2];
-          if (a[3] != std::numeric_limits<int64_t>::min()) sa.minNexthop = a[3];
-          names.emplace_back(ln, b, e - b);
-          as.push_back(sa);
-        }
-        b = e + 1;
-      }
-      prefixes.push_back(std::move(names));
-      at.push_back(std::move(as));
-    }
-    if (used != n_attrs) throw std::invalid_argument("more attribute sets than announcer names");
+    const auto prefixes = prefixLines(prefixes_nl, n_prefixes);
+    const auto at = attrLists(prefixes, attrs, n_attrs);
     const auto r = h->ls.allSourcesSelect(prefixes, at, use_link_metric != 0, nh_words);
-    if (metric) std::copy(r.metric.begin(), r.metric.end(), metric);
-    if (count) std::copy(r.count.begin(), r.count.end(), count);
-    if (nh) std::copy(r.nh.begin(), r.nh.end(), nh);
-    if (links) std::copy(r.links.begin(), r.links.end(), links);
-    if (need) std::copy(r.need.begin(), r.need.end(), need);
-    if (best) std::copy(r.best.begin(), r.best.end(), best);
-    if (installed) std::copy(r.installed.begin(), r.installed.end(), installed);
+    copyOut(r.metric, metric);
+    copyOut(r.count, count);
+    copyOut(r.nh, nh);
+    copyOut(r.links, links);
+    copyOut(r.need, need);
+    copyOut(r.best, best);
+    copyOut(r.installed, installed);
     return 0;
   }, -1);
 }
@@ -582,52 +558,19 @@ int odl_all_sources_select_srmpls(odl_ls* h, const char* prefixes_nl, uint32_t n
     const uint32_t words = h->ls.selectWords();
     if (nh_words_needed) *nh_words_needed = words;
     if (!nh_words) return 0;  // the width only
-    if (n_prefixes && !prefixes_nl) throw std::invalid_argument("null prefix lines");
-    if (n_attrs && !attrs) throw std::invalid_argument("null attributes");
-    std::vector<std::vector<std::string>> prefixes;
-    std::vector<std::vector<odl::LinkState::SelectAttr>> at;
+    const auto prefixes = prefixLines(prefixes_nl, n_prefixes);
     std::vector<std::vector<uint8_t>> prepend;
-    size_t used = 0;
-    for (const auto& ln : splitNl(prefixes_nl ? prefixes_nl : "", n_prefixes)) {
-      std::vector<std::string> names;
-      std::vector<odl::LinkState::SelectAttr> as;
-      std::vector<uint8_t> pp;
-      for (size_t b = 0; b < ln.size();) {  // tab-separated, empty fields skipped
-        size_t e = ln.find('\t', b);
-        if (e == std::string::npos) e = ln.size();
-        if (e > b) {
-          if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than announcer names");
-          const int64_t* a = attrs + 5 * used++;
-          odl::LinkState::SelectAttr sa;
-          sa.pathPreference = a[0];
-          sa.sourcePreference = a[1];
-          sa.distance = a[2];
-          if (a[3] != std::numeric_limits<int64_t>::min()) sa.minNexthop = a[3];
-          if (a[4] != 0 && a[4] != 1) throw std::invalid_argument("the prepend flag is 0 or 1");
-          names.emplace_back(ln, b, e - b);
-          as.push_back(sa);
-          pp.push_back((uint8_t)a[4]);
-        }
-        b = e + 1;
-      }
-      prefixes.push_back(std::move(names));
-      at.push_back(std::move(as));
-      prepend.push_back(std::move(pp));
-    }
-    if (used != n_attrs) throw std::invalid_argument("more attribute sets than announcer names");
+    const auto at = attrLists(prefixes, attrs, n_attrs, &prepend);
     const auto r = h->ls.allSourcesSelectSrMpls(prefixes, at, prepend, use_link_metric != 0, nh_words);
-    auto put = [](const auto& src, auto* dst) {
-      if (dst) std::copy(src.begin(), src.end(), dst);
-    };
-    put(r.entryOffsets, entry_offsets);
-    put(r.metric, metric);
-    put(r.count, count);
-    put(r.links, links);
-    put(r.need, need);
-    put(r.best, best);
-    put(r.dstLinks, dst_links);
-    put(r.dstNh, dst_nh);
-    put(r.installed, installed);
+    copyOut(r.entryOffsets, entry_offsets);
+    copyOut(r.metric, metric);
+    copyOut(r.count, count);
+    copyOut(r.links, links);
+    copyOut(r.need, need);
+    copyOut(r.best, best);
+    copyOut(r.dstLinks, dst_links);
+    copyOut(r.dstNh, dst_nh);
+    copyOut(r.installed, installed);
     return 0;
   }, -1);
 }
@@ -652,15 +595,7 @@ std::vector<std::vector<odl::LinkState::AreaEntry>> areaEntries(const char* pref
     std::vector<odl::LinkState::AreaEntry> es;
     for (size_t i = 0; i < f.size(); i += 2) {
       if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than entries");
-      const int64_t* a = attrs + 4 * used++;
-      odl::LinkState::AreaEntry e;
-      e.node = f[i];
-      e.area = f[i + 1];
-      e.attr.pathPreference = a[0];
-      e.attr.sourcePreference = a[1];
-      e.attr.distance = a[2];
-      if (a[3] != std::numeric_limits<int64_t>::min()) e.attr.minNexthop = a[3];
-      es.push_back(std::move(e));
+      es.push_back(odl::LinkState::AreaEntry{f[i], f[i + 1], attrOf(attrs + 4 * used++)});
     }
     prefixes.push_back(std::move(es));
   }
@@ -690,22 +625,19 @@ int odl_areas_select_policy(odl_ls* const* areas, uint32_t n_areas, const char* 
     if (names_nl) prefixes = areaEntries(prefixes_nl, n_prefixes, attrs, n_attrs);
     const auto r = odl::LinkState::allAreasSelect(ls, prefixes, use_link_metric != 0);
     if (n_global) *n_global = (uint32_t)r.names.size();
-    if (order) std::copy(r.order.begin(), r.order.end(), order);
-    if (nh_words) std::copy(r.words.begin(), r.words.end(), nh_words);
+    copyOut(r.order, order);
+    copyOut(r.words, nh_words);
     if (on_device) *on_device = r.onDevice ? 1 : 0;
     if (!names_nl) return 0;
-    auto give = [](const std::vector<uint32_t>& src, uint32_t* dst) {
-      if (dst) std::copy(src.begin(), src.end(), dst);
-    };
-    give(r.metric, metric);
-    give(r.count, count);
-    give(r.links, links);
-    give(r.need, need);
-    give(r.best, best);
-    give(r.areas, areas_mask);
-    if (installed) std::copy(r.installed.begin(), r.installed.end(), installed);
+    copyOut(r.metric, metric);
+    copyOut(r.count, count);
+    copyOut(r.links, links);
+    copyOut(r.need, need);
+    copyOut(r.best, best);
+    copyOut(r.areas, areas_mask);
+    copyOut(r.installed, installed);
     if (nh)
-      for (uint32_t i = 0; i < n_areas; ++i) give(r.nh[i], nh[i]);
+      for (uint32_t i = 0; i < n_areas; ++i) copyOut(r.nh[i], nh[i]);
     std::string txt;
     for (const auto& nm : r.names) {
       if (nm.find('\n') != std::string::npos)
@@ -759,12 +691,7 @@ int odl_areas_set_attrs(odl_areas_tracker* t, const int64_t* attrs, uint32_t n_a
     for (auto& es : p)
       for (auto& e : es) {
         if (used >= n_attrs) throw std::invalid_argument("fewer attribute sets than entries");
-        const int64_t* a = attrs + 4 * used++;
-        e.attr = odl::LinkState::SelectAttr{};
-        e.attr.pathPreference = a[0];
-        e.attr.sourcePreference = a[1];
-        e.attr.distance = a[2];
-        if (a[3] != std::numeric_limits<int64_t>::min()) e.attr.minNexthop = a[3];
+        e.attr = attrOf(attrs + 4 * used++);
       }
     if (used != n_attrs) throw std::invalid_argument("more attribute sets than entries");
     t->t->setAttrs(p);
@@ -814,20 +741,17 @@ int odl_areas_tracked(odl_areas_tracker* t, const char* nodes_nl, uint32_t n, ui
     // without outputs: the areas' order and words only (what sizes nh)
     const bool query = !metric && !count && !links && !need && !best && !areas_mask && !nh && !installed;
     const auto r = t->t->tracked(query ? std::vector<std::string>{} : splitNl(nodes_nl ? nodes_nl : "", n));
-    if (order) std::copy(r.order.begin(), r.order.end(), order);
-    if (nh_words) std::copy(r.words.begin(), r.words.end(), nh_words);
-    auto give = [](const std::vector<uint32_t>& src, uint32_t* dst) {
-      if (dst) std::copy(src.begin(), src.end(), dst);
-    };
-    give(r.metric, metric);
-    give(r.count, count);
-    give(r.links, links);
-    give(r.need, need);
-    give(r.best, best);
-    give(r.areas, areas_mask);
-    if (installed) std::copy(r.installed.begin(), r.installed.end(), installed);
+    copyOut(r.order, order);
+    copyOut(r.words, nh_words);
+    copyOut(r.metric, metric);
+    copyOut(r.count, count);
+    copyOut(r.links, links);
+    copyOut(r.need, need);
+    copyOut(r.best, best);
+    copyOut(r.areas, areas_mask);
+    copyOut(r.installed, installed);
     if (nh)
-      for (size_t i = 0; i < r.nh.size(); ++i) give(r.nh[i], nh[i]);
+      for (size_t i = 0; i < r.nh.size(); ++i) copyOut(r.nh[i], nh[i]);
     return 0;
   }, -1);
 }
@@ -874,9 +798,9 @@ int odl_select_tracked(odl_ls* h, const char* nodes_nl, uint32_t n, uint32_t nh_
                        uint32_t* metric, uint32_t* count, uint32_t* nh) {
   return guard(h, [&]() -> int {
     const auto r = h->ls.selectTracked(splitNl(nodes_nl ? nodes_nl : "", n), nh_words);
-    if (metric) std::copy(r.metric.begin(), r.metric.end(), metric);
-    if (count) std::copy(r.count.begin(), r.count.end(), count);
-    if (nh) std::copy(r.nh.begin(), r.nh.end(), nh);
+    copyOut(r.metric, metric);
+    copyOut(r.count, count);
+    copyOut(r.nh, nh);
     return 0;
   }, -1);
 }
@@ -902,9 +826,9 @@ int giveView(const odl::LinkState::UcmpView& v, int64_t* weight, uint8_t* status
   if (!wt || !n_wt) throw std::invalid_argument("null output pointer");
   *wt = dupVec(v.wt);
   *n_wt = v.wt.size();
-  if (weight) std::copy(v.weight.begin(), v.weight.end(), weight);
-  if (status) std::copy(v.status.begin(), v.status.end(), status);
-  if (off) std::copy(v.off.begin(), v.off.end(), off);
+  copyOut(v.weight, weight);
+  copyOut(v.status, status);
+  copyOut(v.off, off);
   return 0;
 }
 }  // namespace
@@ -914,8 +838,8 @@ int odl_all_sources_ucmp(odl_ls* h, int algo, const int64_t* leaf_weights, uint3
                          double* engine_ms) {
   return guard(h, [&]() -> int {
     const auto r = h->ls.allSourcesUcmp((odl::UcmpAlgo)algo, leafLists(h->ls, leaf_weights, n_weights));
-    if (weight) std::copy(r.weight.begin(), r.weight.end(), weight);
-    if (status) std::copy(r.status.begin(), r.status.end(), status);
+    copyOut(r.weight, weight);
+    copyOut(r.status, status);
     if (rounds) *rounds = r.rounds;
     if (on_device) *on_device = r.device ? 1 : 0;
     if (engine_ms) *engine_ms = r.engineMs;

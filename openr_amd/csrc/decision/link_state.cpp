@@ -1111,16 +1111,203 @@ std::vector<ospf_digest> LinkState::allSourcesDigestsImpl(bool useLinkMetric) {
     if (rc != OSPF_OK) throw EngineError(rc, ospf_multi_last_error(multi_));
     return out;
   }
-  ospf_sweep_info info{};
-  ospf_sweep_get_info(sweep_, &info);
-  std::vector<uint32_t> roots(info.n_roots);
-  ospf_sweep_roots(sweep_, roots.data());
+  const std::vector<uint32_t> roots = ownedRoots();
   std::vector<ospf_digest> tmp(roots.size());
   const int rc = ospf_sweep_digests_host(sweep_, tmp.data());
   if (rc != OSPF_OK) throw EngineError(rc, ospf_sweep_last_error(sweep_));
   for (size_t i = 0; i < roots.size(); ++i) out[roots[i]] = tmp[i];
   return out;
 }
+
+std::vector<uint32_t> LinkState::ownedRoots() const {
+  ospf_sweep_info info{};
+  ospf_sweep_get_info(sweep_, &info);
+  std::vector<uint32_t> roots(info.n_roots);
+  ospf_sweep_roots(sweep_, roots.data());
+  return roots;
+}
+
+// ---------------------------------------------------------------- select: the shared host steps
+namespace {
+
+using Lists = std::vector<std::vector<uint32_t>>;  // one list per prefix
+
+// the distinct neighbours of a root, ascending: the next-hop bit order (nhWordsFor)
+std::vector<uint32_t> distinctNbrs(const LinkState::Csr& cs, uint32_t root) {
+  std::vector<uint32_t> out;
+  for (uint32_t e = cs.rowPtr[root]; e < cs.rowPtr[root + 1]; ++e) {
+    const uint32_t v = cs.col[e];
+    if (v != root && (out.empty() || out.back() != v)) out.push_back(v);
+  }
+  return out;
+}
+
+// the slot (bit) of neighbour `id` in nbrs, nbrs.size() when it is none
+uint32_t slotOf(const std::vector<uint32_t>& nbrs, uint32_t id) {
+  const auto it = std::lower_bound(nbrs.begin(), nbrs.end(), id);
+  return (uint32_t)((it != nbrs.end() && *it == id ? it : nbrs.end()) - nbrs.begin());
+}
+
+// A root's links as route selection sees them: its distinct neighbours and,
+// per slot, the links r - k getNextHopsThrift emits: up, at the smallest
+// metric r advertises towards k (every up link under hop count)
+struct LinkView {
+  std::vector<uint32_t> nbrs, c;
+};
+LinkView linkView(const LinkState::Csr& cs, uint32_t r, bool useLinkMetric) {
+  LinkView v;
+  v.nbrs = distinctNbrs(cs, r);
+  v.c.assign(v.nbrs.size(), 0);
+  std::vector<uint32_t> minw(v.nbrs.size(), kInf);
+  for (int pass = 0; pass < 2; ++pass)
+    for (uint32_t e = cs.rowPtr[r]; e < cs.rowPtr[r + 1]; ++e) {
+      if (cs.col[e] == r || !cs.edgeUp[e]) continue;
+      const uint32_t k = slotOf(v.nbrs, cs.col[e]);
+      if (!pass) minw[k] = std::min(minw[k], cs.metric[e]);
+      else if (!useLinkMetric || cs.metric[e] == minw[k]) ++v.c[k];
+    }
+  return v;
+}
+
+// next-hop names -> bits of `words` (W of them) by slot in nbrs; onNew(k) for
+// every bit k this call set
+template <class OnNew>
+void setNextHopBits(uint32_t* words, uint32_t W, const std::vector<uint32_t>& nbrs,
+                    const std::unordered_map<std::string, uint32_t>& ids,
+                    const std::unordered_set<std::string>& nextHopNames, OnNew&& onNew) {
+  for (const auto& nhName : nextHopNames) {
+    const uint32_t k = slotOf(nbrs, ids.at(nhName));
+    if (k == nbrs.size() || k / 32 >= W || (words[k / 32] >> (k % 32) & 1u)) continue;
+    words[k / 32] |= 1u << (k % 32);
+    onNew(k);
+  }
+}
+void setNextHopBits(uint32_t* words, uint32_t W, const std::vector<uint32_t>& nbrs,
+                    const std::unordered_map<std::string, uint32_t>& ids,
+                    const std::unordered_set<std::string>& nextHopNames) {
+  setNextHopBits(words, W, nbrs, ids, nextHopNames, [](uint32_t) {});
+}
+
+// the links behind the set bits of `words`: an IP route's next-hop links
+uint32_t linksOf(const uint32_t* words, uint32_t W, const std::vector<uint32_t>& c) {
+  uint32_t n = 0;
+  for (uint32_t k = 0; k < c.size() && k / 32 < W; ++k)
+    if (words[k / 32] >> (k % 32) & 1u) n += c[k];
+  return n;
+}
+
+// createRouteForPrefix's first steps for one root and one prefix of a single
+// area (SpfSolver.cpp:229-244, 649-676, 709-731): the announcers the root
+// reaches, of them the best class S, and S without its drained members
+// unless all are drained (Sf); positions into ann, ascending; d: the distance
+// of each reached announcer. False: none reached.
+struct BestClass {
+  std::vector<Metric> d;
+  std::vector<size_t> S, Sf;
+};
+bool bestClass(const SpfResult& res, const LinkState::Csr& cs, const std::vector<uint32_t>& ann,
+               const std::vector<uint32_t>& pref, BestClass& b) {
+  std::vector<size_t> R;
+  b.d.assign(ann.size(), 0);
+  b.S.clear();
+  b.Sf.clear();
+  uint32_t top = kInf;
+  for (size_t i = 0; i < ann.size(); ++i) {
+    const auto it = res.find(cs.names[ann[i]]);
+    if (it == res.end()) continue;
+    b.d[i] = it->second.metric();
+    R.push_back(i);
+    top = std::min(top, pref[i]);
+  }
+  for (size_t i : R)
+    if (pref[i] == top) b.S.push_back(i);
+  for (size_t i : b.S)
+    if (!cs.noTransit[ann[i]]) b.Sf.push_back(i);
+  if (b.Sf.empty()) b.Sf = b.S;
+  return !R.empty();
+}
+
+// bestNodeArea's node: the smallest id of S (ann ascends), or the root itself
+uint32_t bestOf(const std::vector<size_t>& S, const std::vector<uint32_t>& ann, uint32_t r) {
+  for (size_t i : S)
+    if (ann[i] == r) return r;
+  return ann[S.front()];
+}
+
+// per-prefix lists -> one flat list (and, with `off`, where each prefix starts)
+std::vector<uint32_t> flatten(const Lists& lists, std::vector<uint32_t>* off = nullptr) {
+  std::vector<uint32_t> flat;
+  if (off) off->assign(1, 0);
+  for (const auto& l : lists) {
+    flat.insert(flat.end(), l.begin(), l.end());
+    if (off) off->push_back((uint32_t)flat.size());
+  }
+  return flat;
+}
+
+// rows in the sweep's owned-roots order -> rows by node id, `per` words each
+void scatterOwned(const std::vector<uint32_t>& roots, const std::vector<uint32_t>& src,
+                  std::vector<uint32_t>& dst, size_t per) {
+  for (size_t i = 0; i < roots.size(); ++i)
+    std::copy(src.begin() + i * per, src.begin() + (i + 1) * per, dst.begin() + roots[i] * per);
+}
+
+// rows `ids` of src ([.][cells][from]) -> dst ([ids.size()][cells][to], to >=
+// from: the tail of each cell stays as it is)
+void gatherRows(const std::vector<uint32_t>& ids, size_t cells, const std::vector<uint32_t>& src,
+                size_t from, std::vector<uint32_t>& dst, size_t to) {
+  for (size_t i = 0; i < ids.size(); ++i)
+    for (size_t p = 0; p < cells; ++p)
+      std::copy(src.begin() + (ids[i] * cells + p) * from,
+                src.begin() + (ids[i] * cells + p + 1) * from, dst.begin() + (i * cells + p) * to);
+}
+
+// a route is programmed when it has next-hop links and at least minNexthop
+// of them (SpfSolver.cpp:990-1000)
+bool isInstalled(uint32_t links, uint32_t need) { return links > 0 && need <= links; }
+void markInstalled(const std::vector<uint32_t>& links, const std::vector<uint32_t>& need,
+                   std::vector<uint8_t>& installed) {
+  installed.resize(links.size());
+  for (size_t i = 0; i < links.size(); ++i) installed[i] = isInstalled(links[i], need[i]);
+}
+
+// the next-hop width of a call: nhWords, or `need` when it is 0; one below `need` throws
+constexpr const char* kWidest = " below the widest node's ";
+constexpr const char* kBaseline = " below the baseline's ";
+uint32_t wordsFor(const char* who, uint32_t nhWords, uint32_t need, const char* what) {
+  const uint32_t W = nhWords ? nhWords : need;
+  if (W < need)
+    throw std::invalid_argument(std::string(who) + ": nhWords " + std::to_string(W) + what +
+                                std::to_string(need));
+  return W;
+}
+
+// results of `rows` nodes, P prefixes and W words: nothing reached anywhere
+LinkState::SelectResult selectResult(size_t rows, size_t P, uint32_t W) {
+  LinkState::SelectResult r;
+  r.prefixes = (uint32_t)P;
+  r.words = W;
+  r.metric.assign(rows * P, kInf);
+  r.count.assign(rows * P, 0);
+  r.nh.assign(rows * P * W, 0);
+  return r;
+}
+LinkState::PolicyResult policyResult(size_t rows, size_t P, uint32_t W) {
+  LinkState::PolicyResult r;
+  r.prefixes = (uint32_t)P;
+  r.words = W;
+  r.metric.assign(rows * P, kInf);
+  r.best.assign(rows * P, kInf);
+  for (auto* v : {&r.count, &r.links, &r.need}) v->assign(rows * P, 0);
+  r.nh.assign(rows * P * W, 0);
+  r.installed.assign(rows * P, 0);
+  return r;
+}
+ospf_select_pout pout(LinkState::PolicyResult& r) {
+  return {r.metric.data(), r.count.data(), r.nh.data(), r.links.data(), r.need.data(), r.best.data()};
+}
+
+}  // namespace
 
 uint32_t LinkState::selectWords() {
   snapshot();
@@ -1129,15 +1316,9 @@ uint32_t LinkState::selectWords() {
   return W;
 }
 
-LinkState::SelectResult LinkState::allSourcesSelect(
-    const std::vector<std::vector<std::string>>& prefixes, bool useLinkMetric, uint32_t nhWords) {
-  snapshot();
-  const uint32_t need = selectWords();
-  if (nhWords && nhWords < need)
-    throw std::invalid_argument("allSourcesSelect: nhWords " + std::to_string(nhWords) +
-                                " below the widest node's " + std::to_string(need));
+Lists LinkState::annIds(const std::vector<std::vector<std::string>>& prefixes) const {
   // names -> ids: unknown names dropped, ascending and distinct per prefix
-  std::vector<std::vector<uint32_t>> ann(prefixes.size());
+  Lists ann(prefixes.size());
   for (size_t p = 0; p < prefixes.size(); ++p) {
     for (const auto& nm : prefixes[p]) {
       const auto it = csr_->ids.find(nm);
@@ -1146,30 +1327,28 @@ LinkState::SelectResult LinkState::allSourcesSelect(
     std::sort(ann[p].begin(), ann[p].end());
     ann[p].erase(std::unique(ann[p].begin(), ann[p].end()), ann[p].end());
   }
-  const uint32_t W = nhWords ? nhWords : need;
+  return ann;
+}
+
+LinkState::SelectResult LinkState::allSourcesSelect(
+    const std::vector<std::vector<std::string>>& prefixes, bool useLinkMetric, uint32_t nhWords) {
+  snapshot();
+  const uint32_t W = wordsFor("allSourcesSelect", nhWords, selectWords(), kWidest);
+  const Lists ann = annIds(prefixes);
   return guarded([&] { return allSourcesSelectImpl(ann, useLinkMetric, W); });
 }
 
-LinkState::SelectResult LinkState::allSourcesSelectImpl(
-    const std::vector<std::vector<uint32_t>>& ann, bool useLinkMetric, uint32_t W) {
+LinkState::SelectResult LinkState::allSourcesSelectImpl(const Lists& ann, bool useLinkMetric,
+                                                        uint32_t W) {
   snapshot();
   const size_t V = csr_->names.size(), P = ann.size();
-  SelectResult out;
-  out.prefixes = (uint32_t)P;
-  out.words = W;
-  out.metric.assign(V * P, kInf);
-  out.count.assign(V * P, 0);
-  out.nh.assign(V * P * W, 0);
+  SelectResult out = selectResult(V, P, W);
   if (!V || !P) return out;
   if (hostRun(useLinkMetric)) {
     // the reference loop (SpfSolver.cpp:1058-1086) over getSpfResult of every node
-    std::vector<uint32_t> nbrs;
     for (uint32_t r = 0; r < V; ++r) {
       const SpfResult& res = getSpfResult(csr_->names[r], useLinkMetric);
-      nbrs.clear();  // distinct neighbours, ascending: the bit order (nhWordsFor)
-      for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e)
-        if (csr_->col[e] != r && (nbrs.empty() || nbrs.back() != csr_->col[e]))
-          nbrs.push_back(csr_->col[e]);
+      const std::vector<uint32_t> nbrs = nbrsOf(r);
       for (size_t p = 0; p < P; ++p) {
         Metric shortest = std::numeric_limits<Metric>::max();
         std::vector<uint32_t> minCost;
@@ -1188,23 +1367,16 @@ LinkState::SelectResult LinkState::allSourcesSelectImpl(
         if (minCost.empty()) continue;
         out.metric[r * P + p] = (uint32_t)shortest;
         out.count[r * P + p] = (uint32_t)minCost.size();
-        uint32_t* words = out.nh.data() + (r * P + p) * W;
         for (uint32_t a : minCost)
-          for (const auto& nhName : res.at(csr_->names[a]).nextHops()) {
-            const uint32_t id = csr_->ids.at(nhName);
-            const uint32_t k = (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), id) - nbrs.begin());
-            if (k < nbrs.size() && nbrs[k] == id && k / 32 < W) words[k / 32] |= 1u << (k % 32);
-          }
+          setNextHopBits(out.nh.data() + (r * P + p) * W, W, nbrs, csr_->ids,
+                         res.at(csr_->names[a]).nextHops());
       }
     }
     return out;
   }
   prefetchAllSources(useLinkMetric);
-  std::vector<uint32_t> off(P + 1, 0), nodes;
-  for (size_t p = 0; p < P; ++p) {
-    nodes.insert(nodes.end(), ann[p].begin(), ann[p].end());
-    off[p + 1] = (uint32_t)nodes.size();
-  }
+  std::vector<uint32_t> off;
+  const std::vector<uint32_t> nodes = flatten(ann, &off);
   const ospf_select_table t{(uint32_t)P, off.data(), nodes.data()};
   if (msweep_) {
     const int rc = ospf_msweep_select(msweep_, &t, W, out.metric.data(), out.count.data(),
@@ -1212,19 +1384,13 @@ LinkState::SelectResult LinkState::allSourcesSelectImpl(
     if (rc != OSPF_OK) throw EngineError(rc, ospf_multi_last_error(multi_));
     return out;
   }
-  ospf_sweep_info info{};
-  ospf_sweep_get_info(sweep_, &info);
-  std::vector<uint32_t> roots(info.n_roots);
-  ospf_sweep_roots(sweep_, roots.data());
+  const std::vector<uint32_t> roots = ownedRoots();
   std::vector<uint32_t> m(roots.size() * P), k(roots.size() * P), nh(roots.size() * P * W);
   const int rc = ospf_sweep_select(sweep_, &t, W, m.data(), k.data(), nh.data());
   if (rc != OSPF_OK) throw EngineError(rc, ospf_sweep_last_error(sweep_));
-  for (size_t i = 0; i < roots.size(); ++i) {  // owned-roots order -> node id
-    const size_t r = roots[i];
-    std::copy(m.begin() + i * P, m.begin() + (i + 1) * P, out.metric.begin() + r * P);
-    std::copy(k.begin() + i * P, k.begin() + (i + 1) * P, out.count.begin() + r * P);
-    std::copy(nh.begin() + i * P * W, nh.begin() + (i + 1) * P * W, out.nh.begin() + r * P * W);
-  }
+  scatterOwned(roots, m, out.metric, P);
+  scatterOwned(roots, k, out.count, P);
+  scatterOwned(roots, nh, out.nh, P * W);
   return out;
 }
 
@@ -1393,9 +1559,6 @@ LinkState::AreasResult LinkState::allAreasSelectImpl(
   for (auto* v : {&out.count, &out.links, &out.need, &out.areas}) v->assign(G * P, 0);
   out.installed.assign(G * P, 0);
   if (!G || !P) return out;
-  auto install = [&] {
-    for (size_t i = 0; i < G * P; ++i) out.installed[i] = out.links[i] > 0 && out.need[i] <= out.links[i];
-  };
   // the device path: every area on the engine, on one device of its own
   auto deviceOk = [&] {
     for (LinkState* ls : ar)
@@ -1429,7 +1592,7 @@ LinkState::AreasResult LinkState::allAreasSelectImpl(
       const int rc = ospf_areas_select_policy(&t, &o);
       if (rc == OSPF_OK) {
         out.onDevice = true;
-        install();
+        markInstalled(out.links, out.need, out.installed);
         return out;
       }
       const EngineError err(rc, ospf_sweep_last_error(sw[0]));
@@ -1447,13 +1610,12 @@ LinkState::AreasResult LinkState::allAreasSelectImpl(
     }
   }
   // the host path: the same steps over every area's getSpfResult
-  std::vector<uint32_t> minw;
   for (uint32_t g = 0; g < G; ++g) {
     const std::string& me = out.names[g];
     struct Mine {
       const SpfResult* res = nullptr;
       uint32_t la = kInf;
-      std::vector<uint32_t> nbrs, c;
+      LinkView links;
     };
     std::vector<Mine> mine(A);
     for (size_t a = 0; a < A; ++a) {
@@ -1463,23 +1625,7 @@ LinkState::AreasResult LinkState::allAreasSelectImpl(
       Mine& m = mine[a];
       m.la = it->second;
       m.res = &ls.getSpfResult(me, useLinkMetric);
-      const Csr& cs = *ls.csr_;
-      const uint32_t r = m.la;
-      m.nbrs = ls.nbrsOf(r);
-      // the links r - k getNextHopsThrift emits: up, at the smallest metric r
-      // advertises towards k (every up link under hop count)
-      minw.assign(m.nbrs.size(), kInf);
-      m.c.assign(m.nbrs.size(), 0);
-      auto slot = [&](uint32_t id) {
-        return (uint32_t)(std::lower_bound(m.nbrs.begin(), m.nbrs.end(), id) - m.nbrs.begin());
-      };
-      for (int pass = 0; pass < 2; ++pass)
-        for (uint32_t e = cs.rowPtr[r]; e < cs.rowPtr[r + 1]; ++e) {
-          if (cs.col[e] == r || !cs.edgeUp[e]) continue;
-          const uint32_t k = slot(cs.col[e]);
-          if (!pass) minw[k] = std::min(minw[k], cs.metric[e]);
-          else if (!useLinkMetric || cs.metric[e] == minw[k]) ++m.c[k];
-        }
+      m.links = linkView(*ls.csr_, m.la, useLinkMetric);
     }
     for (size_t p = 0; p < P; ++p) {
       const uint32_t lo = off[p], hi = off[p + 1];
@@ -1538,13 +1684,8 @@ LinkState::AreasResult LinkState::allAreasSelectImpl(
         const uint32_t W = out.words[a];
         uint32_t* words = out.nh[a].data() + ((size_t)m.la * P + p) * W;
         for (const std::string* d : L)
-          for (const auto& nhName : m.res->at(*d).nextHops()) {
-            const uint32_t id = ar[a]->csr_->ids.at(nhName);
-            const uint32_t k = (uint32_t)(std::lower_bound(m.nbrs.begin(), m.nbrs.end(), id) - m.nbrs.begin());
-            if (k < m.nbrs.size() && m.nbrs[k] == id && k / 32 < W) words[k / 32] |= 1u << (k % 32);
-          }
-        for (uint32_t k = 0; k < m.nbrs.size() && k / 32 < W; ++k)
-          if (words[k / 32] >> (k % 32) & 1u) out.links[cell] += m.c[k];
+          setNextHopBits(words, W, m.links.nbrs, ar[a]->csr_->ids, m.res->at(*d).nextHops());
+        out.links[cell] += linksOf(words, W, m.links.c);
         out.count[cell] += (uint32_t)L.size();
         out.areas[cell] |= 1u << a;
       }
@@ -1558,10 +1699,9 @@ LinkState::AreasResult LinkState::allAreasSelectImpl(
         }
     }
   }
-  install();
+  markInstalled(out.links, out.need, out.installed);
   return out;
 }
-
 
 // ---------------------------------------------------------------- the areas tracker
 LinkState::AreasResult LinkState::allAreasSelect(const std::vector<LinkState*>& given,
@@ -1676,8 +1816,7 @@ void LinkState::AreasTracker::pull() {
       std::copy(byg[a].begin() + gid_[a][i] * row, byg[a].begin() + (gid_[a][i] + 1) * row,
                 r.nh[a].begin() + i * row);
   }
-  r.installed.assign(G * P, 0);
-  for (size_t i = 0; i < G * P; ++i) r.installed[i] = r.links[i] > 0 && r.need[i] <= r.links[i];
+  markInstalled(r.links, r.need, r.installed);
   host_ = std::move(r);
 }
 
@@ -1786,7 +1925,7 @@ LinkState::AreasTracker::Delta LinkState::AreasTracker::delta() {
   auto finish = [&] {
     d.installed.resize(d.changes.size());
     for (size_t i = 0; i < d.changes.size(); ++i)
-      d.installed[i] = d.changes[i].links > 0 && d.changes[i].need <= d.changes[i].links;
+      d.installed[i] = isInstalled(d.changes[i].links, d.changes[i].need);
   };
   if (namesMoved(m) || (!st_ && !hostOk_)) {
     baseline();
@@ -1895,8 +2034,7 @@ LinkState::AreasResult LinkState::AreasTracker::tracked(const std::vector<std::s
       }
     }
   }
-  r.installed.assign(n * P, 0);
-  for (size_t i = 0; i < n * P; ++i) r.installed[i] = r.links[i] > 0 && r.need[i] <= r.links[i];
+  markInstalled(r.links, r.need, r.installed);
   return r;
 }
 
@@ -1904,145 +2042,68 @@ LinkState::PolicyResult LinkState::allSourcesSelect(
     const std::vector<std::vector<std::string>>& prefixes,
     const std::vector<std::vector<SelectAttr>>& attrs, bool useLinkMetric, uint32_t nhWords) {
   snapshot();
-  const uint32_t need = selectWords();
-  if (nhWords && nhWords < need)
-    throw std::invalid_argument("allSourcesSelect: nhWords " + std::to_string(nhWords) +
-                                " below the widest node's " + std::to_string(need));
-  std::vector<std::vector<uint32_t>> ann, pref, mnh;
+  const uint32_t W = wordsFor("allSourcesSelect", nhWords, selectWords(), kWidest);
+  Lists ann, pref, mnh;
   policyTable(prefixes, attrs, "allSourcesSelect", ann, pref, mnh);
-  const uint32_t W = nhWords ? nhWords : need;
   return guarded([&] { return allSourcesPolicyImpl(ann, pref, mnh, useLinkMetric, W); });
 }
 
-LinkState::PolicyResult LinkState::allSourcesPolicyImpl(
-    const std::vector<std::vector<uint32_t>>& ann, const std::vector<std::vector<uint32_t>>& pref,
-    const std::vector<std::vector<uint32_t>>& mnh, bool useLinkMetric, uint32_t W) {
+LinkState::PolicyResult LinkState::allSourcesPolicyImpl(const Lists& ann, const Lists& pref,
+                                                        const Lists& mnh, bool useLinkMetric,
+                                                        uint32_t W) {
   snapshot();
   const size_t V = csr_->names.size(), P = ann.size();
-  PolicyResult out;
-  out.prefixes = (uint32_t)P;
-  out.words = W;
-  out.metric.assign(V * P, kInf);
-  out.count.assign(V * P, 0);
-  out.links.assign(V * P, 0);
-  out.need.assign(V * P, 0);
-  out.best.assign(V * P, kInf);
-  out.nh.assign(V * P * W, 0);
-  out.installed.assign(V * P, 0);
+  PolicyResult out = policyResult(V, P, W);
   if (!V || !P) return out;
-  auto install = [&] {
-    for (size_t i = 0; i < V * P; ++i)
-      out.installed[i] = out.links[i] > 0 && out.need[i] <= out.links[i];
-  };
   if (hostRun(useLinkMetric)) {
     // createRouteForPrefix's steps (SpfSolver.cpp:229-244, 649-676, 709-731,
     // 990-1000) over getSpfResult of every node
-    std::vector<uint32_t> nbrs, minw, c;
+    BestClass b;
     for (uint32_t r = 0; r < V; ++r) {
       const SpfResult& res = getSpfResult(csr_->names[r], useLinkMetric);
-      // distinct neighbours, ascending (the bit order), and the links r - k
-      // getNextHopsThrift emits: up, at the smallest metric r advertises
-      // towards k (every up link under hop count)
-      nbrs.clear();
-      for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e)
-        if (csr_->col[e] != r && (nbrs.empty() || nbrs.back() != csr_->col[e]))
-          nbrs.push_back(csr_->col[e]);
-      minw.assign(nbrs.size(), kInf);
-      c.assign(nbrs.size(), 0);
-      auto slot = [&](uint32_t id) {
-        return (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), id) - nbrs.begin());
-      };
-      for (int pass = 0; pass < 2; ++pass)
-        for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e) {
-          if (csr_->col[e] == r || !csr_->edgeUp[e]) continue;
-          const uint32_t k = slot(csr_->col[e]);
-          if (!pass) minw[k] = std::min(minw[k], csr_->metric[e]);
-          else if (!useLinkMetric || csr_->metric[e] == minw[k]) ++c[k];
-        }
+      const LinkView links = linkView(*csr_, r, useLinkMetric);
       for (size_t p = 0; p < P; ++p) {
-        const size_t n = ann[p].size();
-        // reached announcers, then the best class among them
-        std::vector<size_t> R;
-        std::vector<Metric> d(n, 0);
-        for (size_t i = 0; i < n; ++i) {
-          const auto it = res.find(csr_->names[ann[p][i]]);
-          if (it == res.end()) continue;
-          d[i] = it->second.metric();
-          R.push_back(i);
-        }
-        if (R.empty()) continue;
-        uint32_t top = kInf;
-        for (size_t i : R) top = std::min(top, pref[p][i]);
-        std::vector<size_t> S, Sf;
-        for (size_t i : R)
-          if (pref[p][i] == top) S.push_back(i);
-        for (size_t i : S)
-          if (!csr_->noTransit[ann[p][i]]) Sf.push_back(i);
-        if (Sf.empty()) Sf = S;
+        if (!bestClass(res, *csr_, ann[p], pref[p], b)) continue;
         Metric shortest = std::numeric_limits<Metric>::max();
-        for (size_t i : Sf) shortest = std::min(shortest, d[i]);
+        for (size_t i : b.Sf) shortest = std::min(shortest, b.d[i]);
         const size_t cell = r * P + p;
         uint32_t* words = out.nh.data() + cell * W;
-        for (size_t i : Sf) {
+        for (size_t i : b.Sf) {
           out.need[cell] = std::max(out.need[cell], mnh[p][i]);
-          if (d[i] != shortest) continue;
+          if (b.d[i] != shortest) continue;
           ++out.count[cell];
-          for (const auto& nhName : res.at(csr_->names[ann[p][i]]).nextHops()) {
-            const uint32_t k = slot(csr_->ids.at(nhName));
-            if (k < nbrs.size() && nbrs[k] == csr_->ids.at(nhName) && k / 32 < W)
-              words[k / 32] |= 1u << (k % 32);
-          }
+          setNextHopBits(words, W, links.nbrs, csr_->ids, res.at(csr_->names[ann[p][i]]).nextHops());
         }
         out.metric[cell] = (uint32_t)shortest;
-        out.best[cell] = ann[p][S.front()];  // ascending ids: the smallest of S
-        for (size_t i : S)
-          if (ann[p][i] == r) out.best[cell] = r;
-        for (uint32_t k = 0; k < nbrs.size() && k / 32 < W; ++k)
-          if (words[k / 32] >> (k % 32) & 1u) out.links[cell] += c[k];
+        out.best[cell] = bestOf(b.S, ann[p], r);
+        out.links[cell] = linksOf(words, W, links.c);
       }
     }
-    install();
+    markInstalled(out.links, out.need, out.installed);
     return out;
   }
   prefetchAllSources(useLinkMetric);
-  std::vector<uint32_t> off(P + 1, 0), nodes, prefs, mins;
-  for (size_t p = 0; p < P; ++p) {
-    nodes.insert(nodes.end(), ann[p].begin(), ann[p].end());
-    prefs.insert(prefs.end(), pref[p].begin(), pref[p].end());
-    mins.insert(mins.end(), mnh[p].begin(), mnh[p].end());
-    off[p + 1] = (uint32_t)nodes.size();
-  }
+  std::vector<uint32_t> off;
+  const std::vector<uint32_t> nodes = flatten(ann, &off), prefs = flatten(pref), mins = flatten(mnh);
   const ospf_select_ptable t{(uint32_t)P, off.data(), nodes.data(), prefs.data(), mins.data()};
   if (msweep_) {
-    const ospf_select_pout o{out.metric.data(), out.count.data(), out.nh.data(),
-                             out.links.data(),  out.need.data(),  out.best.data()};
+    const ospf_select_pout o = pout(out);
     const int rc = ospf_msweep_select_policy(msweep_, &t, W, &o);
     if (rc != OSPF_OK) throw EngineError(rc, ospf_multi_last_error(multi_));
-    install();
-    return out;
+  } else {
+    const std::vector<uint32_t> roots = ownedRoots();
+    PolicyResult own = policyResult(roots.size(), P, W);  // in owned-roots order
+    const ospf_select_pout o = pout(own);
+    const int rc = ospf_sweep_select_policy(sweep_, &t, W, &o);
+    if (rc != OSPF_OK) throw EngineError(rc, ospf_sweep_last_error(sweep_));
+    scatterOwned(roots, own.metric, out.metric, P);
+    scatterOwned(roots, own.count, out.count, P);
+    scatterOwned(roots, own.nh, out.nh, P * W);
+    scatterOwned(roots, own.links, out.links, P);
+    scatterOwned(roots, own.need, out.need, P);
+    scatterOwned(roots, own.best, out.best, P);
   }
-  ospf_sweep_info info{};
-  ospf_sweep_get_info(sweep_, &info);
-  std::vector<uint32_t> roots(info.n_roots);
-  ospf_sweep_roots(sweep_, roots.data());
-  const size_t n = roots.size();
-  std::vector<uint32_t> m(n * P), k(n * P), nh(n * P * W), li(n * P), ne(n * P), be(n * P);
-  const ospf_select_pout o{m.data(), k.data(), nh.data(), li.data(), ne.data(), be.data()};
-  const int rc = ospf_sweep_select_policy(sweep_, &t, W, &o);
-  if (rc != OSPF_OK) throw EngineError(rc, ospf_sweep_last_error(sweep_));
-  for (size_t i = 0; i < n; ++i) {  // owned-roots order -> node id
-    const size_t r = roots[i];
-    auto put = [&](const std::vector<uint32_t>& src, std::vector<uint32_t>& dst, size_t per) {
-      std::copy(src.begin() + i * per, src.begin() + (i + 1) * per, dst.begin() + r * per);
-    };
-    put(m, out.metric, P);
-    put(k, out.count, P);
-    put(nh, out.nh, P * W);
-    put(li, out.links, P);
-    put(ne, out.need, P);
-    put(be, out.best, P);
-  }
-  install();
+  markInstalled(out.links, out.need, out.installed);
   return out;
 }
 
@@ -2052,11 +2113,8 @@ LinkState::SrMplsResult LinkState::allSourcesSelectSrMpls(
     const std::vector<std::vector<SelectAttr>>& attrs,
     const std::vector<std::vector<uint8_t>>& hasPrepend, bool useLinkMetric, uint32_t nhWords) {
   snapshot();
-  const uint32_t need = selectWords();
-  if (nhWords && nhWords < need)
-    throw std::invalid_argument("allSourcesSelectSrMpls: nhWords " + std::to_string(nhWords) +
-                                " below the widest node's " + std::to_string(need));
-  std::vector<std::vector<uint32_t>> ann, pref, mnh, pos, flags;
+  const uint32_t W = wordsFor("allSourcesSelectSrMpls", nhWords, selectWords(), kWidest);
+  Lists ann, pref, mnh, pos, flags;
   policyTable(prefixes, attrs, "allSourcesSelectSrMpls", ann, pref, mnh, &pos);
   if (hasPrepend.size() != prefixes.size())
     throw std::invalid_argument("allSourcesSelectSrMpls: one prepend list per prefix");
@@ -2066,164 +2124,85 @@ LinkState::SrMplsResult LinkState::allSourcesSelectSrMpls(
       throw std::invalid_argument("allSourcesSelectSrMpls: one prepend flag per announcer");
     for (uint32_t i : pos[p]) flags[p].push_back(hasPrepend[p][i] ? OSPF_SEL_SELF_PREPEND : 0u);
   }
-  const uint32_t W = nhWords ? nhWords : need;
   return guarded([&] { return allSourcesSrMplsImpl(ann, pref, mnh, flags, useLinkMetric, W); });
 }
 
-LinkState::SrMplsResult LinkState::allSourcesSrMplsImpl(
-    const std::vector<std::vector<uint32_t>>& ann, const std::vector<std::vector<uint32_t>>& pref,
-    const std::vector<std::vector<uint32_t>>& mnh, const std::vector<std::vector<uint32_t>>& flags,
-    bool useLinkMetric, uint32_t W) {
+LinkState::SrMplsResult LinkState::allSourcesSrMplsImpl(const Lists& ann, const Lists& pref,
+                                                        const Lists& mnh, const Lists& flags,
+                                                        bool useLinkMetric, uint32_t W) {
   snapshot();
   const size_t V = csr_->names.size(), P = ann.size();
   SrMplsResult out;
   out.prefixes = (uint32_t)P;
   out.words = W;
-  out.entryOffsets.assign(P + 1, 0);
-  for (size_t p = 0; p < P; ++p) {
-    out.entryNodes.insert(out.entryNodes.end(), ann[p].begin(), ann[p].end());
-    out.entryOffsets[p + 1] = (uint32_t)out.entryNodes.size();
-  }
+  out.entryNodes = flatten(ann, &out.entryOffsets);
   const size_t A = out.entryNodes.size();
   out.metric.assign(V * P, kInf);
-  out.count.assign(V * P, 0);
-  out.links.assign(V * P, 0);
-  out.need.assign(V * P, 0);
   out.best.assign(V * P, kInf);
+  for (auto* v : {&out.count, &out.links, &out.need}) v->assign(V * P, 0);
   out.dstLinks.assign(V * A, 0);
   out.dstNh.assign(V * A * W, 0);
   out.installed.assign(V * P, 0);
   if (!V || !P) return out;
-  auto install = [&] {
-    for (size_t i = 0; i < V * P; ++i)
-      out.installed[i] = out.links[i] > 0 && out.need[i] <= out.links[i];
-  };
   // msweep has no SR_MPLS selection: a multi-device LinkState takes the host loop
   if (hostRun(useLinkMetric) || devices_.size() > 1) {
     // createRouteForPrefix's steps, then selectBestPathsSpf's per-destination
     // next hops (SpfSolver.cpp:794-806, 1043-1089) over getSpfResult of every node
-    std::vector<uint32_t> nbrs, minw, c;
+    BestClass b;
     for (uint32_t r = 0; r < V; ++r) {
       const SpfResult& res = getSpfResult(csr_->names[r], useLinkMetric);
-      nbrs.clear();
-      for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e)
-        if (csr_->col[e] != r && (nbrs.empty() || nbrs.back() != csr_->col[e]))
-          nbrs.push_back(csr_->col[e]);
-      minw.assign(nbrs.size(), kInf);
-      c.assign(nbrs.size(), 0);
-      auto slot = [&](uint32_t id) {
-        return (uint32_t)(std::lower_bound(nbrs.begin(), nbrs.end(), id) - nbrs.begin());
-      };
-      for (int pass = 0; pass < 2; ++pass)
-        for (uint32_t e = csr_->rowPtr[r]; e < csr_->rowPtr[r + 1]; ++e) {
-          if (csr_->col[e] == r || !csr_->edgeUp[e]) continue;
-          const uint32_t k = slot(csr_->col[e]);
-          if (!pass) minw[k] = std::min(minw[k], csr_->metric[e]);
-          else if (!useLinkMetric || csr_->metric[e] == minw[k]) ++c[k];
-        }
+      const LinkView links = linkView(*csr_, r, useLinkMetric);
       for (size_t p = 0; p < P; ++p) {
-        const size_t n = ann[p].size();
-        std::vector<size_t> R;
-        std::vector<Metric> d(n, 0);
-        for (size_t i = 0; i < n; ++i) {
-          const auto it = res.find(csr_->names[ann[p][i]]);
-          if (it == res.end()) continue;
-          d[i] = it->second.metric();
-          R.push_back(i);
-        }
-        if (R.empty()) continue;
-        uint32_t top = kInf;
-        for (size_t i : R) top = std::min(top, pref[p][i]);
-        std::vector<size_t> S, Sf, D;
-        for (size_t i : R)
-          if (pref[p][i] == top) S.push_back(i);
-        for (size_t i : S)
-          if (!csr_->noTransit[ann[p][i]]) Sf.push_back(i);
-        if (Sf.empty()) Sf = S;
+        if (!bestClass(res, *csr_, ann[p], pref[p], b)) continue;
         const size_t cell = r * P + p;
-        for (size_t i : Sf) {
+        std::vector<size_t> D;
+        for (size_t i : b.Sf) {
           out.need[cell] = std::max(out.need[cell], mnh[p][i]);
           // filteredBestNodeAreas: the node's own entry with a prepend label leaves
           if (!(ann[p][i] == r && (flags[p][i] & OSPF_SEL_SELF_PREPEND))) D.push_back(i);
         }
-        out.best[cell] = ann[p][S.front()];  // ascending ids: the smallest of S
-        for (size_t i : S)
-          if (ann[p][i] == r) out.best[cell] = r;
+        out.best[cell] = bestOf(b.S, ann[p], r);
         if (D.empty()) continue;
         Metric shortest = std::numeric_limits<Metric>::max();
-        for (size_t i : D) shortest = std::min(shortest, d[i]);
+        for (size_t i : D) shortest = std::min(shortest, b.d[i]);
         out.metric[cell] = (uint32_t)shortest;
         for (size_t i : D) {
-          if (d[i] != shortest) continue;
+          if (b.d[i] != shortest) continue;
           ++out.count[cell];
           const size_t ent = r * A + out.entryOffsets[p] + i;
-          uint32_t* words = out.dstNh.data() + ent * W;
-          for (const auto& nhName : res.at(csr_->names[ann[p][i]]).nextHops()) {
-            const uint32_t id = csr_->ids.at(nhName);
-            const uint32_t k = slot(id);
-            if (k < nbrs.size() && nbrs[k] == id && k / 32 < W && !(words[k / 32] >> (k % 32) & 1u)) {
-              words[k / 32] |= 1u << (k % 32);
-              out.dstLinks[ent] += c[k];
-            }
-          }
+          setNextHopBits(out.dstNh.data() + ent * W, W, links.nbrs, csr_->ids,
+                         res.at(csr_->names[ann[p][i]]).nextHops(),
+                         [&](uint32_t k) { out.dstLinks[ent] += links.c[k]; });
           out.links[cell] += out.dstLinks[ent];
         }
       }
     }
-    install();
+    markInstalled(out.links, out.need, out.installed);
     return out;
   }
   prefetchAllSources(useLinkMetric);
-  std::vector<uint32_t> prefs, mins, fl;
-  for (size_t p = 0; p < P; ++p) {
-    prefs.insert(prefs.end(), pref[p].begin(), pref[p].end());
-    mins.insert(mins.end(), mnh[p].begin(), mnh[p].end());
-    fl.insert(fl.end(), flags[p].begin(), flags[p].end());
-  }
+  const std::vector<uint32_t> prefs = flatten(pref), mins = flatten(mnh), fl = flatten(flags);
   const ospf_select_stable t{(uint32_t)P,  out.entryOffsets.data(), out.entryNodes.data(),
                              prefs.data(), mins.data(),             fl.data()};
-  ospf_sweep_info info{};
-  ospf_sweep_get_info(sweep_, &info);
-  std::vector<uint32_t> roots(info.n_roots);
-  ospf_sweep_roots(sweep_, roots.data());
+  const std::vector<uint32_t> roots = ownedRoots();
   const size_t n = roots.size();
   std::vector<uint32_t> m(n * P), k(n * P), li(n * P), ne(n * P), be(n * P), dl(n * A),
       dn(n * A * W);
   const ospf_select_sout o{m.data(), k.data(), li.data(), ne.data(), be.data(), dl.data(), dn.data()};
   const int rc = ospf_sweep_select_srmpls(sweep_, &t, W, &o);
   if (rc != OSPF_OK) throw EngineError(rc, ospf_sweep_last_error(sweep_));
-  for (size_t i = 0; i < n; ++i) {  // owned-roots order -> node id
-    const size_t r = roots[i];
-    auto put = [&](const std::vector<uint32_t>& src, std::vector<uint32_t>& dst, size_t per) {
-      std::copy(src.begin() + i * per, src.begin() + (i + 1) * per, dst.begin() + r * per);
-    };
-    put(m, out.metric, P);
-    put(k, out.count, P);
-    put(li, out.links, P);
-    put(ne, out.need, P);
-    put(be, out.best, P);
-    put(dl, out.dstLinks, A);
-    put(dn, out.dstNh, A * W);
-  }
-  install();
+  scatterOwned(roots, m, out.metric, P);
+  scatterOwned(roots, k, out.count, P);
+  scatterOwned(roots, li, out.links, P);
+  scatterOwned(roots, ne, out.need, P);
+  scatterOwned(roots, be, out.best, P);
+  scatterOwned(roots, dl, out.dstLinks, A);
+  scatterOwned(roots, dn, out.dstNh, A * W);
+  markInstalled(out.links, out.need, out.installed);
   return out;
 }
 
 // ---------------------------------------------------------------- trackSelect
-std::vector<std::vector<uint32_t>> LinkState::trackAnn() const {
-  // names -> ids as allSourcesSelect: unknown names dropped, ascending, distinct
-  std::vector<std::vector<uint32_t>> ann(trackPrefixes_.size());
-  for (size_t p = 0; p < trackPrefixes_.size(); ++p) {
-    for (const auto& nm : trackPrefixes_[p]) {
-      const auto it = csr_->ids.find(nm);
-      if (it != csr_->ids.end()) ann[p].push_back(it->second);
-    }
-    std::sort(ann[p].begin(), ann[p].end());
-    ann[p].erase(std::unique(ann[p].begin(), ann[p].end()), ann[p].end());
-  }
-  return ann;
-}
-
 void LinkState::trackDropDev() {
   if (selstate_) ospf_selstate_destroy(selstate_);
   selstate_ = nullptr;
@@ -2233,40 +2212,25 @@ void LinkState::trackDropDev() {
 
 void LinkState::trackPull() {
   if (!trackDev_ || !selstate_) return;
-  const size_t V = trackNames_.size(), P = trackPrefixes_.size(), W = trackWords_;
+  const size_t V = trackNames_.size(), P = trackPrefixes_.size();
+  const uint32_t W = trackWords_;
   std::vector<uint32_t> ids(V);
-  for (size_t i = 0; i < V; ++i) ids[i] = (uint32_t)i;
+  std::iota(ids.begin(), ids.end(), 0u);
+  int rc;
   if (trackPolicy_) {
-    PolicyResult r;
-    r.prefixes = (uint32_t)P;
-    r.words = (uint32_t)W;
-    r.metric.assign(V * P, kInf);
-    r.count.assign(V * P, 0);
-    r.links.assign(V * P, 0);
-    r.need.assign(V * P, 0);
-    r.best.assign(V * P, kInf);
-    r.nh.assign(V * P * W, 0);
-    const ospf_select_pout o{r.metric.data(), r.count.data(), r.nh.data(),
-                             r.links.data(),  r.need.data(),  r.best.data()};
-    const int rc = ospf_selstate_copy_policy(selstate_, ids.data(), (uint32_t)V, (uint32_t)W, &o);
-    r.installed.assign(V * P, 0);
-    for (size_t i = 0; i < V * P; ++i) r.installed[i] = r.links[i] > 0 && r.need[i] <= r.links[i];
-    trackDev_ = false;
-    trackHostOk_ = rc == OSPF_OK;
-    if (trackHostOk_) trackHostP_ = std::move(r);
-    return;
+    PolicyResult r = policyResult(V, P, W);
+    const ospf_select_pout o = pout(r);
+    rc = ospf_selstate_copy_policy(selstate_, ids.data(), (uint32_t)V, W, &o);
+    markInstalled(r.links, r.need, r.installed);
+    if (rc == OSPF_OK) trackHostP_ = std::move(r);
+  } else {
+    SelectResult r = selectResult(V, P, W);
+    rc = ospf_selstate_copy(selstate_, ids.data(), (uint32_t)V, W, r.metric.data(), r.count.data(),
+                            r.nh.data());
+    if (rc == OSPF_OK) trackHost_ = std::move(r);
   }
-  SelectResult r;
-  r.prefixes = (uint32_t)P;
-  r.words = (uint32_t)W;
-  r.metric.assign(V * P, kInf);
-  r.count.assign(V * P, 0);
-  r.nh.assign(V * P * W, 0);
-  const int rc = ospf_selstate_copy(selstate_, ids.data(), (uint32_t)V, (uint32_t)W, r.metric.data(),
-                                    r.count.data(), r.nh.data());
   trackDev_ = false;
   trackHostOk_ = rc == OSPF_OK;
-  if (trackHostOk_) trackHost_ = std::move(r);
 }
 
 void LinkState::trackPrime() {
@@ -2279,28 +2243,16 @@ void LinkState::trackPrime() {
   trackHostP_ = PolicyResult{};
   trackAttrsMoved_ = false;
   const uint32_t W = selectWords();
-  std::vector<std::vector<uint32_t>> pann, pref, mnh;
+  Lists pann, pref, mnh;
   if (trackPolicy_) policyTable(trackPrefixes_, trackAttrs_, "trackSelect", pann, pref, mnh);
   if (!hostRun(trackMetric_) && devices_.size() == 1 && V) {
     prefetchAllSources(trackMetric_);
-    std::vector<uint32_t> off(ann.size() + 1, 0), nodes;
-    for (size_t p = 0; p < ann.size(); ++p) {
-      nodes.insert(nodes.end(), ann[p].begin(), ann[p].end());
-      off[p + 1] = (uint32_t)nodes.size();
-    }
+    std::vector<uint32_t> off;
+    const std::vector<uint32_t> nodes = flatten(ann, &off), prefs = flatten(pref), mins = flatten(mnh);
     const ospf_select_table t{(uint32_t)ann.size(), off.data(), nodes.data()};
-    int rc;
-    if (trackPolicy_) {
-      std::vector<uint32_t> prefs, mins;
-      for (size_t p = 0; p < ann.size(); ++p) {
-        prefs.insert(prefs.end(), pref[p].begin(), pref[p].end());
-        mins.insert(mins.end(), mnh[p].begin(), mnh[p].end());
-      }
-      const ospf_select_ptable pt{t.n_prefixes, off.data(), nodes.data(), prefs.data(), mins.data()};
-      rc = ospf_selstate_create_policy(engine_, &pt, &selstate_);
-    } else {
-      rc = ospf_selstate_create(engine_, &t, &selstate_);
-    }
+    const ospf_select_ptable pt{t.n_prefixes, off.data(), nodes.data(), prefs.data(), mins.data()};
+    int rc = trackPolicy_ ? ospf_selstate_create_policy(engine_, &pt, &selstate_)
+                          : ospf_selstate_create(engine_, &t, &selstate_);
     if (rc != OSPF_OK) throw EngineError(rc, ospf_last_error(engine_));
     rc = ospf_selstate_prime(selstate_, sweep_);
     if (rc != OSPF_OK) {
@@ -2334,7 +2286,7 @@ void LinkState::trackSelect(const std::vector<std::vector<std::string>>& prefixe
 void LinkState::trackSelect(const std::vector<std::vector<std::string>>& prefixes,
                             const std::vector<std::vector<SelectAttr>>& attrs, bool useLinkMetric) {
   snapshot();
-  std::vector<std::vector<uint32_t>> ann, pref, mnh;
+  Lists ann, pref, mnh;
   policyTable(prefixes, attrs, "trackSelect", ann, pref, mnh);  // the argument checks
   trackPrefixes_ = prefixes;
   trackAttrs_ = attrs;
@@ -2348,7 +2300,7 @@ void LinkState::setTrackedAttrs(const std::vector<std::vector<SelectAttr>>& attr
   if (!tracking_ || !trackPolicy_)
     throw std::logic_error("setTrackedAttrs: no table tracked with attributes (trackSelect)");
   snapshot();
-  std::vector<std::vector<uint32_t>> ann, pref, mnh;
+  Lists ann, pref, mnh;
   policyTable(trackPrefixes_, attrs, "setTrackedAttrs", ann, pref, mnh);
   trackAttrs_ = attrs;
   trackAttrsMoved_ = true;
@@ -2357,70 +2309,97 @@ void LinkState::setTrackedAttrs(const std::vector<std::vector<SelectAttr>>& attr
   // knows that the state's table is still the snapshot's (trackAttrsMoved_)
 }
 
-LinkState::PolicyDelta LinkState::policyDelta() {
-  if (!tracking_ || !trackPolicy_)
-    throw std::logic_error("policyDelta: no table tracked with attributes (trackSelect)");
-  return guarded([&] { return policyDeltaImpl(); });
-}
+// What selectDelta and policyDelta differ in: the records, the engine's update
+// call, the host recompute and the scalar columns compared
+struct LinkState::PlainTrack {
+  using Delta = SelectDelta;
+  using Result = SelectResult;
+  using Rec = ospf_select_change;
+  static constexpr auto update = ospf_selstate_update;
+  static Result& host(LinkState& ls) { return ls.trackHost_; }
+  static Result recompute(LinkState& ls, uint32_t W) {
+    return ls.allSourcesSelectImpl(ls.trackAnn(), ls.trackMetric_, W);
+  }
+  static bool differ(const Result& a, const Result& b, size_t i) {
+    return a.metric[i] != b.metric[i] || a.count[i] != b.count[i];
+  }
+  static SelectChange change(const Rec& r) { return {r.root, r.prefix, r.metric, r.count}; }
+  static SelectChange change(uint32_t v, uint32_t p, const Result& n, size_t i) {
+    return {v, p, n.metric[i], n.count[i]};
+  }
+};
+struct LinkState::PolicyTrack {
+  using Delta = PolicyDelta;
+  using Result = PolicyResult;
+  using Rec = ospf_select_pchange;
+  static constexpr auto update = ospf_selstate_update_policy;
+  static Result& host(LinkState& ls) { return ls.trackHostP_; }
+  static Result recompute(LinkState& ls, uint32_t W) {
+    Lists ann, pref, mnh;
+    ls.policyTable(ls.trackPrefixes_, ls.trackAttrs_, "policyDelta", ann, pref, mnh);
+    return ls.allSourcesPolicyImpl(ann, pref, mnh, ls.trackMetric_, W);
+  }
+  static bool differ(const Result& a, const Result& b, size_t i) {
+    return a.metric[i] != b.metric[i] || a.count[i] != b.count[i] || a.links[i] != b.links[i] ||
+           a.need[i] != b.need[i] || a.best[i] != b.best[i];
+  }
+  static PolicyChange change(const Rec& r) {
+    return {r.root, r.prefix, r.metric, r.count, r.links, r.need, r.best, r.installed};
+  }
+  static PolicyChange change(uint32_t v, uint32_t p, const Result& n, size_t i) {
+    return {v, p, n.metric[i], n.count[i], n.links[i], n.need[i], n.best[i], n.installed[i]};
+  }
+};
 
-LinkState::PolicyDelta LinkState::policyDeltaImpl() {
+template <class T>
+typename T::Delta LinkState::trackedDelta() {
   snapshot();
-  PolicyDelta out;
+  typename T::Delta out;
   const size_t V = csr_->names.size(), P = trackPrefixes_.size();
   const uint32_t W = selectWords();
   out.words = W;
-  if (csr_->names != trackNames_ || (!trackDev_ && !trackHostOk_)) {
+  const auto anew = [&] {
     trackPrime();
     out.full = true;
     return out;
-  }
+  };
+  // the ids were renumbered, or no baseline survived (a device error that
+  // took it along): everything anew
+  if (csr_->names != trackNames_ || (!trackDev_ && !trackHostOk_)) return anew();
   const bool dev = !hostRun(trackMetric_) && devices_.size() == 1;
   if (dev && trackDev_) {
     prefetchAllSources(trackMetric_);  // re-sweeps when the version moved
-    if (trackAttrsMoved_) {
+    if (trackPolicy_ && trackAttrsMoved_) {  // setTrackedAttrs since the last delta
       // the node names are the tracked ones here, so the ids are the state's
-      std::vector<std::vector<uint32_t>> ann, pref, mnh;
+      Lists ann, pref, mnh;
       policyTable(trackPrefixes_, trackAttrs_, "policyDelta", ann, pref, mnh);
-      std::vector<uint32_t> prefs, mins;
-      for (size_t p = 0; p < ann.size(); ++p) {
-        prefs.insert(prefs.end(), pref[p].begin(), pref[p].end());
-        mins.insert(mins.end(), mnh[p].begin(), mnh[p].end());
-      }
+      const std::vector<uint32_t> prefs = flatten(pref), mins = flatten(mnh);
       const int rc = ospf_selstate_set_policy(selstate_, prefs.data(), mins.data());
       if (rc != OSPF_OK) throw EngineError(rc, ospf_selstate_last_error(selstate_));
     }
     uint32_t cap = 1024, capReb = 64, n = 0, nReb = 0;
-    std::vector<ospf_select_pchange> recs;
+    std::vector<typename T::Rec> recs;
     for (;;) {
       recs.resize(cap);
       out.nh.assign((size_t)cap * W, 0);
       out.rebased.assign(capReb, 0);
-      const int rc = ospf_selstate_update_policy(selstate_, sweep_, W, recs.data(), out.nh.data(), cap,
-                                                 &n, out.rebased.data(), capReb, &nReb);
+      const int rc = T::update(selstate_, sweep_, W, recs.data(), out.nh.data(), cap, &n,
+                               out.rebased.data(), capReb, &nReb);
       if (rc == OSPF_OK) break;
       if (rc != OSPF_E_RANGE) throw EngineError(rc, ospf_selstate_last_error(selstate_));
       cap = std::max(cap, n);  // the state is unchanged: the same call, large enough
       capReb = std::max(capReb, nReb);
     }
-    out.changes.resize(n);
-    for (uint32_t i = 0; i < n; ++i)
-      out.changes[i] = PolicyChange{recs[i].root, recs[i].prefix, recs[i].metric, recs[i].count,
-                                    recs[i].links, recs[i].need,   recs[i].best,   recs[i].installed};
+    for (uint32_t i = 0; i < n; ++i) out.changes.push_back(T::change(recs[i]));
     out.nh.resize((size_t)n * W);
     out.rebased.resize(nReb);
     std::sort(out.rebased.begin(), out.rebased.end());
   } else {
     if (trackDev_) trackPull();  // the host takes over with the device's baseline
-    if (!trackHostOk_) {
-      trackPrime();
-      out.full = true;
-      return out;
-    }
+    if (!trackHostOk_) return anew();
     trackDropDev();
-    std::vector<std::vector<uint32_t>> ann, pref, mnh;
-    policyTable(trackPrefixes_, trackAttrs_, "policyDelta", ann, pref, mnh);
-    PolicyResult now = allSourcesPolicyImpl(ann, pref, mnh, trackMetric_, W);
-    const PolicyResult& was = trackHostP_;
+    typename T::Result now = T::recompute(*this, W);
+    const typename T::Result& was = T::host(*this);
     for (uint32_t v = 0; v < V; ++v) {
       if (nbrsOf(v) != trackNbrs_[v]) {
         out.rebased.push_back(v);
@@ -2428,18 +2407,15 @@ LinkState::PolicyDelta LinkState::policyDeltaImpl() {
       }
       for (size_t p = 0; p < P; ++p) {
         const size_t i = v * P + p;
-        bool ch = now.metric[i] != was.metric[i] || now.count[i] != was.count[i] ||
-                  now.links[i] != was.links[i] || now.need[i] != was.need[i] ||
-                  now.best[i] != was.best[i];
+        bool ch = T::differ(now, was, i);
         for (uint32_t w = 0; w < std::max(W, was.words) && !ch; ++w)
           ch = (w < W ? now.nh[i * W + w] : 0u) != (w < was.words ? was.nh[i * was.words + w] : 0u);
         if (!ch) continue;
-        out.changes.push_back(PolicyChange{v, (uint32_t)p, now.metric[i], now.count[i], now.links[i],
-                                           now.need[i], now.best[i], now.installed[i]});
+        out.changes.push_back(T::change(v, (uint32_t)p, now, i));
         out.nh.insert(out.nh.end(), now.nh.begin() + i * W, now.nh.begin() + (i + 1) * W);
       }
     }
-    trackHostP_ = std::move(now);
+    T::host(*this) = std::move(now);
   }
   trackWords_ = W;
   for (uint32_t v : out.rebased) trackNbrs_[v] = nbrsOf(v);
@@ -2448,52 +2424,37 @@ LinkState::PolicyDelta LinkState::policyDeltaImpl() {
   return out;
 }
 
+LinkState::PolicyDelta LinkState::policyDelta() {
+  if (!tracking_ || !trackPolicy_)
+    throw std::logic_error("policyDelta: no table tracked with attributes (trackSelect)");
+  return guarded([&] { return trackedDelta<PolicyTrack>(); });
+}
+
 LinkState::PolicyResult LinkState::policyTracked(const std::vector<std::string>& nodes,
                                                  uint32_t nhWords) {
   if (!tracking_ || !trackPolicy_)
     throw std::logic_error("policyTracked: no table tracked with attributes (trackSelect)");
   if (!trackDev_ && !trackHostOk_) throw std::logic_error("policyTracked: no baseline (policyDelta)");
-  const uint32_t W = nhWords ? nhWords : trackWords_;
-  if (W < trackWords_)
-    throw std::invalid_argument("policyTracked: nhWords " + std::to_string(W) +
-                                " below the baseline's " + std::to_string(trackWords_));
+  const uint32_t W = wordsFor("policyTracked", nhWords, trackWords_, kBaseline);
   const auto ids = trackIds(nodes, "policyTracked");
   return guarded([&] {
-    const size_t n = ids.size(), P = trackPrefixes_.size();
-    PolicyResult r;
-    r.prefixes = (uint32_t)P;
-    r.words = W;
-    r.metric.assign(n * P, kInf);
-    r.count.assign(n * P, 0);
-    r.links.assign(n * P, 0);
-    r.need.assign(n * P, 0);
-    r.best.assign(n * P, kInf);
-    r.nh.assign(n * P * W, 0);
-    r.installed.assign(n * P, 0);
+    const size_t P = trackPrefixes_.size();
+    PolicyResult r = policyResult(ids.size(), P, W);
     if (trackDev_) {
-      const ospf_select_pout o{r.metric.data(), r.count.data(), r.nh.data(),
-                               r.links.data(),  r.need.data(),  r.best.data()};
-      const int rc = ospf_selstate_copy_policy(selstate_, ids.data(), (uint32_t)n, W, &o);
+      const ospf_select_pout o = pout(r);
+      const int rc = ospf_selstate_copy_policy(selstate_, ids.data(), (uint32_t)ids.size(), W, &o);
       if (rc != OSPF_OK) throw EngineError(rc, ospf_selstate_last_error(selstate_));
     } else {
       if (!trackHostOk_) throw std::logic_error("policyTracked: the baseline was lost (policyDelta)");
       const PolicyResult& h = trackHostP_;
-      for (size_t i = 0; i < n; ++i) {
-        const size_t v = ids[i];
-        auto put = [&](const std::vector<uint32_t>& src, std::vector<uint32_t>& dst) {
-          std::copy(src.begin() + v * P, src.begin() + (v + 1) * P, dst.begin() + i * P);
-        };
-        put(h.metric, r.metric);
-        put(h.count, r.count);
-        put(h.links, r.links);
-        put(h.need, r.need);
-        put(h.best, r.best);
-        for (size_t p = 0; p < P; ++p)
-          std::copy(h.nh.begin() + (v * P + p) * h.words, h.nh.begin() + (v * P + p + 1) * h.words,
-                    r.nh.begin() + (i * P + p) * W);
-      }
+      gatherRows(ids, P, h.metric, 1, r.metric, 1);
+      gatherRows(ids, P, h.count, 1, r.count, 1);
+      gatherRows(ids, P, h.links, 1, r.links, 1);
+      gatherRows(ids, P, h.need, 1, r.need, 1);
+      gatherRows(ids, P, h.best, 1, r.best, 1);
+      gatherRows(ids, P, h.nh, h.words, r.nh, W);
     }
-    for (size_t i = 0; i < n * P; ++i) r.installed[i] = r.links[i] > 0 && r.need[i] <= r.links[i];
+    markInstalled(r.links, r.need, r.installed);
     return r;
   });
 }
@@ -2501,75 +2462,7 @@ LinkState::PolicyResult LinkState::policyTracked(const std::vector<std::string>&
 LinkState::SelectDelta LinkState::selectDelta() {
   if (!tracking_) throw std::logic_error("selectDelta: no tracked table (trackSelect)");
   if (trackPolicy_) throw std::logic_error("selectDelta: the table is tracked with attributes (policyDelta)");
-  return guarded([&] { return selectDeltaImpl(); });
-}
-
-LinkState::SelectDelta LinkState::selectDeltaImpl() {
-  snapshot();
-  SelectDelta out;
-  const size_t V = csr_->names.size(), P = trackPrefixes_.size();
-  const uint32_t W = selectWords();
-  out.words = W;
-  // the ids were renumbered, or no baseline survived (a device error that
-  // took it along): everything anew
-  if (csr_->names != trackNames_ || (!trackDev_ && !trackHostOk_)) {
-    trackPrime();
-    out.full = true;
-    return out;
-  }
-  const bool dev = !hostRun(trackMetric_) && devices_.size() == 1;
-  if (dev && trackDev_) {
-    prefetchAllSources(trackMetric_);  // re-sweeps when the version moved
-    uint32_t cap = 1024, capReb = 64, n = 0, nReb = 0;
-    std::vector<ospf_select_change> recs;
-    for (;;) {
-      recs.resize(cap);
-      out.nh.assign((size_t)cap * W, 0);
-      out.rebased.assign(capReb, 0);
-      const int rc = ospf_selstate_update(selstate_, sweep_, W, recs.data(), out.nh.data(), cap, &n,
-                                          out.rebased.data(), capReb, &nReb);
-      if (rc == OSPF_OK) break;
-      if (rc != OSPF_E_RANGE) throw EngineError(rc, ospf_selstate_last_error(selstate_));
-      cap = std::max(cap, n);  // the state is unchanged: the same call, large enough
-      capReb = std::max(capReb, nReb);
-    }
-    out.changes.resize(n);
-    for (uint32_t i = 0; i < n; ++i)
-      out.changes[i] = SelectChange{recs[i].root, recs[i].prefix, recs[i].metric, recs[i].count};
-    out.nh.resize((size_t)n * W);
-    out.rebased.resize(nReb);
-    std::sort(out.rebased.begin(), out.rebased.end());
-  } else {
-    if (trackDev_) trackPull();  // the host takes over with the device's baseline
-    if (!trackHostOk_) {
-      trackPrime();
-      out.full = true;
-      return out;
-    }
-    trackDropDev();
-    SelectResult now = allSourcesSelectImpl(trackAnn(), trackMetric_, W);
-    const SelectResult& was = trackHost_;
-    for (uint32_t v = 0; v < V; ++v) {
-      if (nbrsOf(v) != trackNbrs_[v]) {
-        out.rebased.push_back(v);
-        continue;
-      }
-      for (size_t p = 0; p < P; ++p) {
-        const size_t i = v * P + p;
-        bool ch = now.metric[i] != was.metric[i] || now.count[i] != was.count[i];
-        for (uint32_t w = 0; w < std::max(W, was.words) && !ch; ++w)
-          ch = (w < W ? now.nh[i * W + w] : 0u) != (w < was.words ? was.nh[i * was.words + w] : 0u);
-        if (!ch) continue;
-        out.changes.push_back(SelectChange{v, (uint32_t)p, now.metric[i], now.count[i]});
-        out.nh.insert(out.nh.end(), now.nh.begin() + i * W, now.nh.begin() + (i + 1) * W);
-      }
-    }
-    trackHost_ = std::move(now);
-  }
-  trackWords_ = W;
-  for (uint32_t v : out.rebased) trackNbrs_[v] = nbrsOf(v);
-  trackVersion_ = snapVersion_;
-  return out;
+  return guarded([&] { return trackedDelta<PlainTrack>(); });
 }
 
 LinkState::SelectResult LinkState::selectTracked(const std::vector<std::string>& nodes,
@@ -2578,41 +2471,22 @@ LinkState::SelectResult LinkState::selectTracked(const std::vector<std::string>&
   if (trackPolicy_)
     throw std::logic_error("selectTracked: the table is tracked with attributes (policyTracked)");
   if (!trackDev_ && !trackHostOk_) throw std::logic_error("selectTracked: no baseline (selectDelta)");
-  const uint32_t W = nhWords ? nhWords : trackWords_;
-  if (W < trackWords_)
-    throw std::invalid_argument("selectTracked: nhWords " + std::to_string(W) +
-                                " below the baseline's " + std::to_string(trackWords_));
-  std::vector<uint32_t> ids;
-  for (const auto& nm : nodes) {
-    const auto it = std::lower_bound(trackNames_.begin(), trackNames_.end(), nm);
-    if (it == trackNames_.end() || *it != nm)
-      throw std::invalid_argument("selectTracked: unknown node " + nm);
-    ids.push_back((uint32_t)(it - trackNames_.begin()));
-  }
+  const uint32_t W = wordsFor("selectTracked", nhWords, trackWords_, kBaseline);
+  const auto ids = trackIds(nodes, "selectTracked");
   return guarded([&] {
-    const size_t n = ids.size(), P = trackPrefixes_.size();
-    SelectResult r;
-    r.prefixes = (uint32_t)P;
-    r.words = W;
-    r.metric.assign(n * P, kInf);
-    r.count.assign(n * P, 0);
-    r.nh.assign(n * P * W, 0);
+    const size_t P = trackPrefixes_.size();
+    SelectResult r = selectResult(ids.size(), P, W);
     if (trackDev_) {
-      const int rc = ospf_selstate_copy(selstate_, ids.data(), (uint32_t)n, W, r.metric.data(),
-                                        r.count.data(), r.nh.data());
+      const int rc = ospf_selstate_copy(selstate_, ids.data(), (uint32_t)ids.size(), W,
+                                        r.metric.data(), r.count.data(), r.nh.data());
       if (rc != OSPF_OK) throw EngineError(rc, ospf_selstate_last_error(selstate_));
       return r;
     }
     if (!trackHostOk_) throw std::logic_error("selectTracked: the baseline was lost (selectDelta)");
     const SelectResult& h = trackHost_;
-    for (size_t i = 0; i < n; ++i) {
-      const size_t v = ids[i];
-      std::copy(h.metric.begin() + v * P, h.metric.begin() + (v + 1) * P, r.metric.begin() + i * P);
-      std::copy(h.count.begin() + v * P, h.count.begin() + (v + 1) * P, r.count.begin() + i * P);
-      for (size_t p = 0; p < P; ++p)
-        std::copy(h.nh.begin() + (v * P + p) * h.words, h.nh.begin() + (v * P + p + 1) * h.words,
-                  r.nh.begin() + (i * P + p) * W);
-    }
+    gatherRows(ids, P, h.metric, 1, r.metric, 1);
+    gatherRows(ids, P, h.count, 1, r.count, 1);
+    gatherRows(ids, P, h.nh, h.words, r.nh, W);
     return r;
   });
 }
@@ -3060,14 +2934,7 @@ const NodeSpfResult& SpfResult::at(const std::string& node) const {
   return it->second;
 }
 
-std::vector<uint32_t> LinkState::nbrsOf(uint32_t root) const {
-  std::vector<uint32_t> out;
-  for (uint32_t e = csr_->rowPtr[root]; e < csr_->rowPtr[root + 1]; ++e) {
-    const uint32_t v = csr_->col[e];
-    if (v != root && (out.empty() || out.back() != v)) out.push_back(v);
-  }
-  return out;
-}
+std::vector<uint32_t> LinkState::nbrsOf(uint32_t root) const { return distinctNbrs(*csr_, root); }
 
 const SpfResult& LinkState::getSpfResultImpl(const std::string& node, bool useLinkMetric) {
   auto& memo = useLinkMetric ? memoMetric_ : memoHops_;

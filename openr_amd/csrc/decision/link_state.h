@@ -963,6 +963,7 @@ class LinkState {
   void ensureEngine();
   void dropSweep();
   bool sweepHas(bool useLinkMetric) const;
+  std::vector<uint32_t> ownedRoots() const;  // the roots of sweep_, in its row order
   // copy rows of roots (all owned by the current sweep) into dist / nh (W words)
   void sweepRows(const std::vector<uint32_t>& roots, uint32_t W, std::vector<uint32_t>& dist,
                  std::vector<uint32_t>& nh);
@@ -1060,6 +1061,9 @@ class LinkState {
                                     const std::vector<std::vector<uint32_t>>& mnh,
                                     const std::vector<std::vector<uint32_t>>& flags,
                                     bool useLinkMetric, uint32_t W);
+  // names -> ids per prefix: unknown names dropped, ascending and distinct
+  std::vector<std::vector<uint32_t>> annIds(
+      const std::vector<std::vector<std::string>>& prefixes) const;
   // names -> ids (unknown names dropped with their attributes, the first
   // occurrence counts, ascending), class ranks and clamped thresholds; `pos`
   // (may be null): each kept entry's position in its prefix's given list
@@ -1087,7 +1091,6 @@ class LinkState {
   bool trackAttrsMoved_ = false;   // setTrackedAttrs since the last policyDelta
   std::vector<std::vector<SelectAttr>> trackAttrs_;  // parallel to trackPrefixes_
   PolicyResult trackHostP_;        // the host baseline of a policy table
-  PolicyDelta policyDeltaImpl();
   std::vector<std::vector<std::string>> trackPrefixes_;  // by name: ids move with the name set
   std::vector<std::string> trackNames_;                  // node names of the baseline
   std::vector<std::vector<uint32_t>> trackNbrs_;         // their distinct neighbours (bit order)
@@ -1096,11 +1099,16 @@ class LinkState {
   bool trackDev_ = false;   // the baseline is the device state's
   bool trackHostOk_ = false;  // the baseline is trackHost_
   SelectResult trackHost_;
-  std::vector<std::vector<uint32_t>> trackAnn() const;  // the table by id, current snapshot
+  // the table by id, current snapshot
+  std::vector<std::vector<uint32_t>> trackAnn() const { return annIds(trackPrefixes_); }
   void trackPrime();                                    // the current snapshot as the baseline
   void trackPull();   // the device baseline into trackHost_ (before the engine goes)
   void trackDropDev();
-  SelectDelta selectDeltaImpl();
+  // selectDelta / policyDelta: one walk, T = PlainTrack or PolicyTrack
+  struct PlainTrack;
+  struct PolicyTrack;
+  template <class T>
+  typename T::Delta trackedDelta();
   // ---- allSourcesUcmp ----
   uint64_t trackVersion_ = 0;  // snapVersion_ of the tracked selection
   bool ucmpDev_ = false;       // the result is the device state's

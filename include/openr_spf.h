@@ -31,7 +31,8 @@
  * the last failure. One context per LinkState (area); a context is not
  * thread-safe (the reference calls SPF from the single Decision thread,
  * openr/Main.cpp:515-527). Out-of-contract inputs (metric 0, possible u32
- * distance overflow, > OSPF_MAX_ROOT_NEIGHBORS distinct root neighbours)
+ * distance overflow, > OSPF_MAX_ROOT_NEIGHBORS distinct root neighbours,
+ * > OSPF_MAX_PARALLEL_LINKS entries from one node to one neighbour)
  * return OSPF_E_RANGE; there is no CPU fallback.
  */
 #ifndef OPENR_SPF_H
@@ -52,6 +53,12 @@ extern "C" {
 
 #define OSPF_DIST_INF 0xFFFFFFFFu
 #define OSPF_MAX_ROOT_NEIGHBORS 8192u /* nh words <= 256 */
+/* The largest parallel group: CSR entries u -> v of one row towards one
+ * neighbour, up or down (a down link may come up in place). ospf_load_graph
+ * and ospf_update_rows refuse a larger one with OSPF_E_RANGE, so c(r, k) --
+ * the links of a next hop k of root r, see `links` of ospf_sweep_select_policy
+ * -- always fits the 16 bits the selection kernels keep per slot. */
+#define OSPF_MAX_PARALLEL_LINKS 65535u
 #define OSPF_MAX_IGNORED_PER_RUN 2048u
 
 /* flags for ospf_sssp_batch* */
@@ -694,7 +701,11 @@ int ospf_sweep_select(ospf_sweep* sw, const ospf_select_table* table, uint32_t n
  *                  route: the sum of c(r, k) over the set bits k of nh, c as
  *                  ospf_selstate_ucmp defines it (up links r - k at the
  *                  smallest metric r advertises on an up link to k; every up
- *                  link under OSPF_HOP_COUNT), from the loaded graph;
+ *                  link under OSPF_HOP_COUNT), from the loaded graph. The sum
+ *                  is plain and exact: no c(r, k) is capped, because a graph
+ *                  with more than OSPF_MAX_PARALLEL_LINKS (65,535) entries
+ *                  r -> k is refused at load (OSPF_E_RANGE), never answered
+ *                  with a smaller count;
  *   need   [n][P]  the largest min_nexthop over S' (not over L: the reference
  *                  takes it over allNodeAreas, :693-707); 0 when R is empty.
  *                  The route is withheld iff need > links and links > 0

@@ -1525,7 +1525,7 @@ int ospf_load_graph(ospf_ctx* c, const ospf_csr* csr, uint64_t version) {
     };
     for (uint32_t u = lo; u < hi && rc == OSPF_OK; ++u) {
       const uint32_t b = csr->row_ptr[u], e1 = csr->row_ptr[u + 1];
-      uint32_t row_max = 0, ndn = 0;
+      uint32_t row_max = 0, ndn = 0, par = 0;
       if (e1 < b || e1 > E) {
         bad(OSPF_E_INVAL, "row_ptr not monotone");
         break;
@@ -1535,6 +1535,12 @@ int ospf_load_graph(ospf_ctx* c, const ospf_csr* csr, uint64_t version) {
         const uint32_t v = csr->col[e];
         if (v >= V) { bad(OSPF_E_INVAL, "col out of range"); break; }
         if (e > b && csr->col[e - 1] > v) { bad(OSPF_E_INVAL, "rows must be sorted by col"); break; }
+        // the selection kernels keep a slot's link count in 16 bits (build_links)
+        par = e > b && csr->col[e - 1] == v ? par + 1 : 1;
+        if (par > OSPF_MAX_PARALLEL_LINKS) {
+          bad(OSPF_E_RANGE, "more than OSPF_MAX_PARALLEL_LINKS parallel links to one neighbour");
+          break;
+        }
         const uint32_t t = csr->twin[e];
         if (t >= E || csr->twin[t] != e || csr->col[t] != u || t < csr->row_ptr[v] ||
             t >= csr->row_ptr[v + 1] || csr->link_id[t] != csr->link_id[e]) {
@@ -3132,10 +3138,13 @@ int ospf_update_rows(ospf_ctx* c, const ospf_csr* csr, const uint32_t* rows, uin
     grow_tot += x.grow;
     max_deg = std::max(max_deg, len);
     ord.resize(len);
-    for (uint32_t j = 0; j < len; ++j) {
+    for (uint32_t j = 0, par = 0; j < len; ++j) {
       const uint32_t e = b + j, v = csr->col[e], t = csr->twin[e];
       if (v >= V) return fail(c, OSPF_E_INVAL, "col out of range");
       if (j && csr->col[e - 1] > v) return fail(c, OSPF_E_INVAL, "rows must be sorted by col");
+      par = j && csr->col[e - 1] == v ? par + 1 : 1;  // as ospf_load_graph
+      if (par > OSPF_MAX_PARALLEL_LINKS)
+        return fail(c, OSPF_E_RANGE, "more than OSPF_MAX_PARALLEL_LINKS parallel links to one neighbour");
       if (t >= E || csr->twin[t] != e || csr->col[t] != u || !row_ok(v) || t < rp[v] ||
           t >= rp[v + 1] || csr->link_id[t] != csr->link_id[e])
         return fail(c, OSPF_E_INVAL, "twin/link_id inconsistent");

@@ -17,9 +17,11 @@
 // advertises on an up link to k, every up link under hop count (as
 // ucmp_links_kernel has them) -- are built once per root in LDS from the
 // root's CSR row: atomicMin of the metric, then a count where it is met, then
-// packed to u16 saturating at 0xFFFF. An entry's `links` is the sum of c over
-// its set next-hop bits. Every word of a wanted output is written once by
-// plain vector stores; no memset, no global atomics, no scratch.
+// packed to u16 (exact: the load refuses a parallel group of more than
+// OSPF_MAX_PARALLEL_LINKS = 0xFFFF entries, so the pack's cap is never
+// reached). An entry's `links` is the sum of c over its set next-hop bits.
+// Every word of a wanted output is written once by plain vector stores; no
+// memset, no global atomics, no scratch.
 //
 // Out of scope (include/openr_spf.h says so too): K_SHORTEST_DISTANCE_2 and
 // PER_AREA_SHORTEST_DISTANCE, BGP metric vectors. (SR_MPLS per-destination next

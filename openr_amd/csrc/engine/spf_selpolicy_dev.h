@@ -272,6 +272,11 @@ __device__ __forceinline__ uint32_t policy_by_words(const Table& t,
 // c[0 .. ns) of root r into LDS as u16 (the first ns halves of `lds`); lds
 // holds 2 * a.cap words. Block-wide, with barriers. `a`: a kernel's arguments
 // with the loaded graph's row_ptr / colx / w / didx, hop and cap (LDS slots).
+// A count always fits its half: a slot counts entries of one parallel group,
+// and the load (ospf_load_graph, ospf_update_rows) refuses a group of more
+// than OSPF_MAX_PARALLEL_LINKS = 0xFFFF entries with OSPF_E_RANGE. The min()
+// of the pack below is therefore never the smaller side; `links` is the plain
+// sum of c(r, k) that include/openr_spf.h defines.
 template <class Args>
 __device__ __forceinline__ void build_links(const Args& a, uint32_t r, uint32_t ns,
                                             uint32_t* lds) {
